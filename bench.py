@@ -15,8 +15,15 @@ N>1: one process per GPU (torch.distributed over RCCL), points sharded by
 index range, scalars seeded per rank (BASELINE.md scheme) — total work is
 fixed at 2^24 points => "scaling": "strong".
 
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline
+figure needs: set up, warm up, time the K steps, optionally write the last
+timed step's result (--dump-outputs DIR) and print the result line.  Every
+other leg (roofline/per-phase timings, NTT, composed wrap step, BLS12-381,
+keccak/trie, batch-prove, CPU baseline) runs only with --full, where the
+--no-* switches still select among them.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--msm-log2 24]
-                       [--ntt-log2 24] [--check]
+                       [--dump-outputs DIR] [--full [--ntt-log2 24]] [--check]
 """
 import argparse
 import json
@@ -68,6 +75,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--msm-log2", type=int, default=24)
     ap.add_argument("--ntt-log2", type=int, default=24)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs: MSM roofline and "
+                         "per-phase timings, NTT, composed wrap step, "
+                         "BLS12-381/keccak/trie, batch-prove and the CPU "
+                         "baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result of the "
+                         "last timed step to DIR/msm_result.npy (float64, "
+                         "one value per byte of the 64-byte affine point)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ntt", action="store_true")
     ap.add_argument("--no-bls", action="store_true")
@@ -82,6 +98,8 @@ def main():
                          "(BASELINE.md reporting range); prints its own "
                          "JSON line and exits")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.sweep:
         import ethrex_amd
@@ -195,7 +213,6 @@ def main():
         dist.barrier()
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    bucket_ms = []
     if world == 1:
         # pipelined steps: the sort chain of step k+1 overlaps the compute
         # chain of step k on a second HIP stream (msm_run_async); all K
@@ -215,8 +232,6 @@ def main():
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     assert pipelined_last == first, "pipelined result != sync result"
-    plan.run()  # one sync step to populate per-phase event timings
-    bucket_ms.append(plan.last_times()["bucket_acc_ms"])
     if world > 1:
         import torch
         t = torch.tensor([dt], device="cuda")
@@ -226,53 +241,70 @@ def main():
     ms_per_step = dt * 1000.0 / args.steps
     value = point_adds(n_total) / (dt / args.steps)
 
-    # ---- roofline for the dominant kernel (bucket accumulation) ----
-    # The kernel is VALU-ISSUE bound (254-bit Montgomery multiplication is
-    # carry-free v_mad_u64_u32 column work; BASELINE.md names VALU as the
-    # MSM roofline axis), so the headline fraction is measured add-rate
-    # against the SIMD issue-rate ceiling:
-    #   peak adds/s = SIMDs * (1 wave-inst / 2 cyc) * clk * 64 lanes / I_add
-    # I_add = 3100 lane-instructions per mixed add, counted from the
-    # llvm-objdump disassembly of the k_bucket_acc<17,signed> main loop
-    # (gfx950: 1024 SIMD-32s, wave64 VALU issue = 2 cyc/inst, ~2.4 GHz).
-    # HBM is reported as the secondary axis with algorithmic bytes.
-    INST_PER_ADD = 3100
-    SIMDS, CLK = 1024, 2.4e9
-    valu_peak_adds = SIMDS * (CLK / 2.0) * 64 / INST_PER_ADD
-    avg_bucket_ms = sum(bucket_ms) / len(bucket_ms)
-    kernel_adds = MSM_WINDOWS * shard  # reduction adds land in other kernels
-    kernel_adds_per_s = kernel_adds / (avg_bucket_ms / 1000.0)
-    # algorithmic HBM bytes/launch: NWIN*shard gathers of a 72-B point +
-    # 4-B sorted value, plus NBUCKETS 144-B XYZZ bucket writes
-    alg_bytes = MSM_WINDOWS * shard * 76 + (MSM_WINDOWS << MSM_IB) * 144
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the
+        # 64-byte affine G1 point (x || y, 32-byte big-endian each).  Every
+        # byte is stored as one float64, which is exact, so two builds can
+        # be compared element for element.
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "msm_result.npy"),
+                np.frombuffer(pipelined_last, dtype=np.uint8)
+                .astype(np.float64))
+
     hbm_peak = 8.0e12
-    roofline = {
-        "bound": "valu",
-        "kernel": "k_bucket_acc",
-        "achieved": kernel_adds_per_s,
-        "peak": valu_peak_adds,
-        "unit": "point_adds/s",
-        "frac": kernel_adds_per_s / valu_peak_adds,
-        "inst_per_add": INST_PER_ADD,
-        # measured per-launch HBM bytes (rocprofv3 FETCH_SIZE+WRITE_SIZE,
-        # profiles/r02_summary.md PMC pass; 1.5x gather overfetch from
-        # random 72-B point reads vs 128-B lines) for the default 2^24
-        # 1-GPU config; null for other shapes
-        "traffic": (28.95e9 if (args.msm_log2 == 24 and shard == n_total)
-                    else None),
-        "hbm_secondary": {
-            "achieved": alg_bytes / (avg_bucket_ms / 1000.0),
-            "peak": hbm_peak,
-            "frac": (alg_bytes / (avg_bucket_ms / 1000.0)) / hbm_peak,
-            "unit": "B/s",
-        },
-        "note": "VALU-issue bound; PMC evidence in profiles/ "
-                "(r01: ACTIVE_INST_VALU 38.8%, memory-wait 3.7%)",
-    }
+    roofline = None
+    phase_ms = None
+    if args.full:
+        plan.run()  # one sync step to populate per-phase event timings
+        phase_ms = {k: round(v, 3) for k, v in plan.last_times().items()}
+        bucket_ms = [plan.last_times()["bucket_acc_ms"]]
+        # ---- roofline for the dominant kernel (bucket accumulation) ----
+        # The kernel is VALU-ISSUE bound (254-bit Montgomery multiplication is
+        # carry-free v_mad_u64_u32 column work; BASELINE.md names VALU as the
+        # MSM roofline axis), so the headline fraction is measured add-rate
+        # against the SIMD issue-rate ceiling:
+        #   peak adds/s = SIMDs * (1 wave-inst / 2 cyc) * clk * 64 lanes / I_add
+        # I_add = 3100 lane-instructions per mixed add, counted from the
+        # llvm-objdump disassembly of the k_bucket_acc<17,signed> main loop
+        # (gfx950: 1024 SIMD-32s, wave64 VALU issue = 2 cyc/inst, ~2.4 GHz).
+        # HBM is reported as the secondary axis with algorithmic bytes.
+        INST_PER_ADD = 3100
+        SIMDS, CLK = 1024, 2.4e9
+        valu_peak_adds = SIMDS * (CLK / 2.0) * 64 / INST_PER_ADD
+        avg_bucket_ms = sum(bucket_ms) / len(bucket_ms)
+        kernel_adds = MSM_WINDOWS * shard  # reduction adds land in other kernels
+        kernel_adds_per_s = kernel_adds / (avg_bucket_ms / 1000.0)
+        # algorithmic HBM bytes/launch: NWIN*shard gathers of a 72-B point +
+        # 4-B sorted value, plus NBUCKETS 144-B XYZZ bucket writes
+        alg_bytes = MSM_WINDOWS * shard * 76 + (MSM_WINDOWS << MSM_IB) * 144
+        roofline = {
+            "bound": "valu",
+            "kernel": "k_bucket_acc",
+            "achieved": kernel_adds_per_s,
+            "peak": valu_peak_adds,
+            "unit": "point_adds/s",
+            "frac": kernel_adds_per_s / valu_peak_adds,
+            "inst_per_add": INST_PER_ADD,
+            # measured per-launch HBM bytes (rocprofv3 FETCH_SIZE+WRITE_SIZE,
+            # profiles/r02_summary.md PMC pass; 1.5x gather overfetch from
+            # random 72-B point reads vs 128-B lines) for the default 2^24
+            # 1-GPU config; null for other shapes
+            "traffic": (28.95e9 if (args.msm_log2 == 24 and shard == n_total)
+                        else None),
+            "hbm_secondary": {
+                "achieved": alg_bytes / (avg_bucket_ms / 1000.0),
+                "peak": hbm_peak,
+                "frac": (alg_bytes / (avg_bucket_ms / 1000.0)) / hbm_peak,
+                "unit": "B/s",
+            },
+            "note": "VALU-issue bound; PMC evidence in profiles/ "
+                    "(r01: ACTIVE_INST_VALU 38.8%, memory-wait 3.7%)",
+        }
 
     # ---- NTT secondary leg (rank 0, single GPU, replicas-only path) ----
     ntt = None
-    if rank == 0 and not args.no_ntt:
+    if args.full and rank == 0 and not args.no_ntt:
         m = 1 << args.ntt_log2
         nplan = ethrex_amd.NttPlan(m)
         nplan.upload(ethrex_amd.gen_fr(43, m))
@@ -329,8 +361,6 @@ def main():
                                "n": m2}
             np2.destroy()
 
-    phase_ms = {k: round(v, 3) for k, v in plan.last_times().items()}
-
     # ---- composed wrap-step leg (BASELINE config 5: "full synthetic-
     # witness block proof (MSM+NTT pipeline) at 2^26 constraints") ----
     # One wrap step = forward NTT of the 2^26-element witness vector +
@@ -341,7 +371,7 @@ def main():
     # shard).  The NTT transforms its own output every step, so scalars
     # differ step to step — nothing inside the timed region is cached.
     pipeline = None
-    if not args.no_pipeline:
+    if args.full and not args.no_pipeline:
         pm = 1 << args.pipeline_log2
         plo, phi = shard_range(pm, n_gpus, rank)
         nplan2 = ethrex_amd.NttPlan(pm)
@@ -395,7 +425,7 @@ def main():
     # 4096-point G1 MSM the sequencer computes per blob,
     # crates/common/crypto/kzg.rs:208-230; rank 0, single GPU) ----
     bls = None
-    if rank == 0 and not args.no_bls:
+    if args.full and rank == 0 and not args.no_bls:
         bp = ethrex_amd.BlsMsmPlan(4096)
         bp.gen_points(0)
         bp.precompute()  # fixed-base table: setup points fixed across blobs
@@ -533,7 +563,7 @@ def main():
     # (GPU batched-keccak node hashing + trie linking) followed by the
     # wrap-shaped NTT -> on-device handoff -> MSM at 2^22 ----
     batch_prove = None
-    if rank == 0 and not args.no_bls:
+    if args.full and rank == 0 and not args.no_bls:
         import os.path as _p
 
         from ethrex_amd import witness as _W
@@ -565,7 +595,7 @@ def main():
         }
 
     cpu_baseline = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         cpu_baseline = cpu_baseline_leg()
 
     plan.destroy()
