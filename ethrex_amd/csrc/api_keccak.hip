@@ -28,6 +28,7 @@ struct em_keccak_plan {
     uint8_t *d_out = nullptr;
     hipEvent_t ev[2];
     double last_ms = 0;
+    bool ran = false;         // d_out holds the digests of the current upload
 };
 
 extern "C" int ethrex_mi355_keccak_plan_create(size_t max_bytes, size_t max_n,
@@ -75,6 +76,7 @@ extern "C" int ethrex_mi355_keccak_upload(em_keccak_plan *p,
     HIP_TRY(hipMemcpy(p->d_offs, offsets, (n + 1) * 8,
                       hipMemcpyHostToDevice));
     p->n = n;
+    p->ran = false;
     return EM_OK;
 }
 
@@ -88,6 +90,7 @@ extern "C" int ethrex_mi355_keccak_run(em_keccak_plan *p) {
     float ms;
     HIP_TRY(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
     p->last_ms = ms;
+    p->ran = true;
     return EM_OK;
 }
 
@@ -100,6 +103,17 @@ extern "C" int ethrex_mi355_keccak_download(em_keccak_plan *p, uint8_t *out) {
 extern "C" int ethrex_mi355_keccak_last_ms(em_keccak_plan *p, double *ms) {
     if (!p || !ms) return EM_ERR_INPUT;
     *ms = p->last_ms;
+    return EM_OK;
+}
+
+// device pointer to the digests of the last run — the wrap-binding handoff:
+// ethrex_mi355_ntt_fill_from_digests expands them on device, no PCIe hop
+extern "C" int ethrex_mi355_keccak_device_digests(em_keccak_plan *p,
+                                                  const void **ptr,
+                                                  size_t *n) {
+    if (!p || !ptr || !p->ran) return EM_ERR_INPUT;
+    *ptr = p->d_out;
+    if (n) *n = p->n;
     return EM_OK;
 }
 

@@ -14,6 +14,7 @@
 #include "em_api_common.h"
 #include "../../include/ethrex_mi355.h"
 #include "ntt_kernels.h"
+#include "keccak_kernels.h"   // k_keccak_pair / k_wrap_expand (witness fill)
 
 using namespace em;
 
@@ -48,6 +49,11 @@ struct em_ntt_plan {
     uint32_t *d_err = nullptr;
     hipEvent_t ev[4];
     double last_ms[3] = {0, 0, 0};
+    uint64_t *d_tree = nullptr;   // fill_from_digests: two ping-pong halves
+    size_t tree_cap = 0;          //   of tree_cap digests each
+    hipEvent_t ev_fill[2];
+    bool ev_fill_ok = false;
+    double last_fill_ms = 0;
 };
 
 // build w2k powers on host and launch k_gen_twiddles: tw[j] = w^j, j < count
@@ -272,6 +278,11 @@ extern "C" int ethrex_mi355_ntt_plan_destroy(em_ntt_plan *p) {
     (void)hipFree(p->d_twrow2_inv);
     (void)hipFree(p->d_ninv);
     (void)hipFree(p->d_err);
+    (void)hipFree(p->d_tree);
+    if (p->ev_fill_ok) {
+        (void)hipEventDestroy(p->ev_fill[0]);
+        (void)hipEventDestroy(p->ev_fill[1]);
+    }
     delete p;
     return EM_OK;
 }
@@ -286,6 +297,64 @@ extern "C" int ethrex_mi355_ntt_upload(em_ntt_plan *p, const uint8_t *elems32) {
     uint32_t err;
     HIP_TRY(hipMemcpy(&err, p->d_err, 4, hipMemcpyDeviceToHost));
     return err ? EM_ERR_INPUT : EM_OK;
+}
+
+// wrap vector v1: expand m device-resident keccak digests into
+// the plan's n resident elements — pairwise keccak tree to the root R
+// (~log2 m launches on ping-pong scratch), then one k_wrap_expand lane per
+// four elements writing fe4m straight into d_data.  Nothing crosses PCIe
+// but the 32 domain bytes (a kernel argument).
+extern "C" int ethrex_mi355_ntt_fill_from_digests(em_ntt_plan *p,
+                                                  const void *d_digests32,
+                                                  size_t m,
+                                                  const uint8_t domain[32]) {
+    if (!p || !d_digests32 || !domain || m == 0) return EM_ERR_INPUT;
+    size_t cap = (m + 1) / 2;
+    if (m > 1 && cap > p->tree_cap) {
+        (void)hipFree(p->d_tree);
+        p->d_tree = nullptr;
+        p->tree_cap = 0;
+        HIP_TRY(hipMalloc((void **)&p->d_tree, 2 * cap * 32));
+        p->tree_cap = cap;
+    }
+    if (!p->ev_fill_ok) {
+        HIP_TRY(hipEventCreate(&p->ev_fill[0]));
+        hipError_t e = hipEventCreate(&p->ev_fill[1]);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(p->ev_fill[0]);
+            return hip_fail(e, "ntt_fill_from_digests");
+        }
+        p->ev_fill_ok = true;
+    }
+    wrap_domain dom;
+    memcpy(dom.v, domain, 32);
+    HIP_TRY(hipEventRecord(p->ev_fill[0], 0));
+    const uint64_t *src = (const uint64_t *)d_digests32;
+    int which = 0;
+    for (size_t len = m; len > 1; len = (len + 1) / 2) {
+        uint64_t *dst = p->d_tree + (which ? p->tree_cap * 4 : 0);
+        hipLaunchKernelGGL(k_keccak_pair, dim3(blocks_for((len + 1) / 2, 256)),
+                           dim3(256), 0, 0, src, dst, len);
+        src = dst;
+        which ^= 1;
+    }
+    hipLaunchKernelGGL(k_wrap_expand, dim3(blocks_for((p->n + 3) / 4, 256)),
+                       dim3(256), 0, 0, (const uint64_t *)d_digests32, src,
+                       (uint64_t)m, dom, p->d_data, p->n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(p->ev_fill[1], 0));
+    HIP_TRY(hipDeviceSynchronize());
+    p->cur = 0;
+    float ms;
+    HIP_TRY(hipEventElapsedTime(&ms, p->ev_fill[0], p->ev_fill[1]));
+    p->last_fill_ms = ms;
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_ntt_last_fill_ms(em_ntt_plan *p, double *ms) {
+    if (!p || !ms) return EM_ERR_INPUT;
+    *ms = p->last_fill_ms;
+    return EM_OK;
 }
 
 extern "C" int ethrex_mi355_ntt_run(em_ntt_plan *p, int inverse) {

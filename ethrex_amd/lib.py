@@ -33,7 +33,8 @@ for _f in ("device_count", "set_device", "bn254_g1_add", "bn254_g1_mul",
            "msm_last_times", "msm_combine", "msm_scalars_from_ntt",
            "ntt_device_data",
            "ntt_plan_create", "ntt_plan_destroy", "ntt_upload", "ntt_run",
-           "ntt_download", "ntt_last_times"):
+           "ntt_download", "ntt_last_times", "ntt_fill_from_digests",
+           "ntt_last_fill_ms", "keccak_device_digests"):
     getattr(_lib, f"ethrex_mi355_{_f}").restype = ctypes.c_int
 
 
@@ -261,6 +262,24 @@ class NttPlan:
         t = (ctypes.c_double * 3)()
         _check(_lib.ethrex_mi355_ntt_last_times(self._p, t), "ntt_last_times")
         return {"bitrev_ms": t[0], "stages_ms": t[1], "total_ms": t[2]}
+
+    def fill_from_digests(self, keccak_plan, domain: bytes):
+        """witness binding: fill the n resident elements with wrap vector
+        v1 (witness.wrap_vector) expanded ON DEVICE from the keccak plan's
+        resident digests — replaces upload(); nothing crosses PCIe."""
+        if len(domain) != 32:
+            raise HipCoreError(EM_ERR_INPUT,
+                               "fill_from_digests: domain must be 32 bytes")
+        ptr, m = keccak_plan.device_digests()
+        _check(_lib.ethrex_mi355_ntt_fill_from_digests(
+            self._p, ptr, ctypes.c_size_t(m), _buf(domain)),
+            "ntt_fill_from_digests")
+
+    def last_fill_ms(self) -> float:
+        ms = ctypes.c_double(0)
+        _check(_lib.ethrex_mi355_ntt_last_fill_ms(self._p, ctypes.byref(ms)),
+               "ntt_last_fill_ms")
+        return ms.value
 
     def destroy(self):
         if self._p:
@@ -537,6 +556,16 @@ class KeccakPlan:
         _check(_lib.ethrex_mi355_keccak_last_ms(self._p, ctypes.byref(ms)),
                "keccak_last_ms")
         return ms.value
+
+    def device_digests(self):
+        """(device pointer, n) of the last run's 32-byte digests; valid
+        until the next upload/destroy (the wrap-binding handoff)."""
+        ptr = ctypes.c_void_p()
+        nn = ctypes.c_size_t(0)
+        _check(_lib.ethrex_mi355_keccak_device_digests(
+            self._p, ctypes.byref(ptr), ctypes.byref(nn)),
+            "keccak_device_digests")
+        return ptr, nn.value
 
     def destroy(self):
         if self._p:

@@ -98,10 +98,23 @@ class Mi355Backend:
     non-vendored zkVM — SURVEY.md §8c — so the proof-OBJECT is this
     core's composition output, carried through the §8f row-3 wire)."""
 
-    def __init__(self, msm_log2=16, ntt_log2=12, device=0):
+    BINDINGS = ("seed", "witness")
+
+    def __init__(self, msm_log2=16, ntt_log2=12, device=0, binding="seed"):
+        # binding: how the composition's input vector is derived.
+        #   "seed"    — gen_fr over the first 8 bytes of the statement
+        #               commitment (host-generated, uploaded);
+        #   "witness" — wrap vector v1 (witness.wrap_vector): expanded on
+        #               device from EVERY witness node digest, so any node
+        #               byte changes the proof.  Witness-less inputs have
+        #               no digests and keep the seed path.
+        if binding not in self.BINDINGS:
+            raise BackendError(f"mi355: unknown binding {binding!r} "
+                               f"(expected one of {self.BINDINGS})")
         self.msm_log2 = msm_log2
         self.ntt_log2 = ntt_log2
         self.device = device
+        self.binding = binding
 
     def prover_type(self) -> str:
         # reuses Exec semantics for coordinator keying (no on-chain
@@ -116,9 +129,11 @@ class Mi355Backend:
             hashlib.sha256(self.serialize_input(input_data)).digest()[:8],
             "little")
 
-    def _gpu_hash_batch(self, msgs):
+    def _gpu_hash_batch(self, msgs, keep=None):
         """batched keccak over the device KeccakPlan (the witness nodes'
-        bulk hashing — §8f row 4)."""
+        bulk hashing — §8f row 4).  With a `keep` list the plan is appended
+        to it instead of destroyed: its device-resident digests feed the
+        witness binding (the caller destroys it)."""
         import ethrex_amd as ea
         offs = [0]
         buf = bytearray()
@@ -130,14 +145,22 @@ class Mi355Backend:
             kp.upload(bytes(buf), offs)
             kp.run()
             out = kp.download()
-        finally:
+        except BaseException:
             kp.destroy()
+            raise
+        if keep is None:
+            kp.destroy()
+        else:
+            keep.append(kp)
         return [out[32 * i:32 * i + 32] for i in range(len(msgs))]
 
     def execute(self, input_data):
         """The witness-validation statement, with the node hashing on the
         GPU (block_execution_witness.rs rebuild semantics); witness-less
         plumbing inputs keep the serialize-only behavior."""
+        return self._execute(input_data, None)
+
+    def _execute(self, input_data, keep):
         wit = _witness_of(input_data)
         if wit is None:
             self.serialize_input(input_data)
@@ -147,15 +170,22 @@ class Mi355Backend:
             raise BackendError("mi355: no GPU visible (no CPU fallback)")
         ea.set_device(self.device)
         from . import witness as W
-        return W.validate_witness(wit[0], wit[1], wit[2],
-                                  self._gpu_hash_batch)
+        return W.validate_witness(
+            wit[0], wit[1], wit[2],
+            lambda msgs: self._gpu_hash_batch(msgs, keep))
 
     def prove(self, input_data, proof_format: str):
         import ethrex_amd as ea
         if ea.device_count() < 1:
             raise BackendError("mi355: no GPU visible (no CPU fallback)")
         ea.set_device(self.device)
-        statement = self.execute(input_data)
+        kplans = [] if self.binding == "witness" else None
+        try:
+            statement = self._execute(input_data, kplans)
+        except BaseException:
+            for kp in kplans or ():
+                kp.destroy()
+            raise
         if statement is not None:
             # the proof binds to the STATEMENT (initial state root +
             # linked-witness commitment), not to a hash of the input JSON
@@ -173,7 +203,13 @@ class Mi355Backend:
         nplan = ea.NttPlan(n)
         try:
             plan.gen_points(0)
-            nplan.upload(ea.gen_fr(seed, n))
+            if kplans:
+                # witness binding: the statement pass hashed every state
+                # node in ONE batch, whose digests are still in HBM
+                nplan.fill_from_digests(
+                    kplans[-1], bytes.fromhex(statement["commitment"]))
+            else:
+                nplan.upload(ea.gen_fr(seed, n))
             nplan.run(False)
             plan.scalars_from_ntt(nplan, 0)
             msm_out = plan.run()
@@ -181,6 +217,8 @@ class Mi355Backend:
         finally:
             plan.destroy()
             nplan.destroy()
+            for kp in kplans or ():
+                kp.destroy()
         proof = {"msm": msm_out,
                  "ntt_digest": hashlib.sha256(ntt_out).digest()}
         if statement is not None:

@@ -233,6 +233,60 @@ def validate_witness(state_nodes, headers_rlp, first_block_number: int,
     }
 
 
+# BN254 scalar modulus r
+FR_MODULUS = int(
+    "21888242871839275222246405745257275088548364400416034343698204186575808495617")
+
+
+def wrap_root(hashes) -> bytes:
+    """Pairwise keccak256 tree root over the digests; an odd last element
+    is promoted to the next level unchanged.  One digest is its own root."""
+    level = list(hashes)
+    if not level:
+        raise ValueError("wrap_vector: no digests")
+    while len(level) > 1:
+        nxt = [keccak256(level[2 * j] + level[2 * j + 1])
+               for j in range(len(level) // 2)]
+        if len(level) & 1:
+            nxt.append(level[-1])
+        level = nxt
+    return level[0]
+
+
+def wrap_vector(hashes, domain: bytes, n: int) -> bytes:
+    """Wrap vector v1: the n = 2^k NTT/MSM input elements
+    derived from EVERY witness node digest — the host restatement of the
+    device expansion (`NttPlan.fill_from_digests`).  Returns n x 32-byte
+    big-endian canonical Fr elements.
+
+    Block j absorbs the single rate-136 block
+        domain || root || le64(m) || le64(j) || hashes[j mod m]
+    (112 bytes, original-Keccak padding), applies one keccak-f1600, and
+    yields elements 4j..4j+3 from state bytes 0..127, each 32-byte slice
+    read big-endian and reduced mod r (from_be_bytes_mod_order)."""
+    from .keccak import keccak_f1600
+    m = len(hashes)
+    if len(domain) != 32 or any(len(h) != 32 for h in hashes):
+        raise ValueError("wrap_vector: domain and digests are 32 bytes")
+    if n < 1 or n & (n - 1):
+        raise ValueError("wrap_vector: n must be a power of two")
+    head = domain + wrap_root(hashes) + m.to_bytes(8, "little")
+    out = bytearray()
+    for j in range((n + 3) // 4):
+        blk = bytearray(head + j.to_bytes(8, "little") + hashes[j % m])
+        blk += b"\x00" * (136 - len(blk))
+        blk[112] ^= 0x01
+        blk[135] ^= 0x80
+        st = [int.from_bytes(blk[8 * i:8 * i + 8], "little")
+              for i in range(17)] + [0] * 8
+        keccak_f1600(st)
+        sq = b"".join(st[i].to_bytes(8, "little") for i in range(16))
+        for t in range(min(4, n - 4 * j)):
+            e = int.from_bytes(sq[32 * t:32 * t + 32], "big") % FR_MODULUS
+            out += e.to_bytes(32, "big")
+    return bytes(out)
+
+
 def load_witness_fixture(path):
     """Load the committed hoodi witness fixture (tests/golden/*.json.gz,
     extracted from the reference's fixtures/cache/rpc_prover cache)."""

@@ -147,6 +147,10 @@ int ethrex_mi355_keccak_upload(em_keccak_plan *plan, const uint8_t *msgs,
 int ethrex_mi355_keccak_run(em_keccak_plan *plan);
 int ethrex_mi355_keccak_download(em_keccak_plan *plan, uint8_t *out32);
 int ethrex_mi355_keccak_last_ms(em_keccak_plan *plan, double *ms);
+/* device pointer to the n 32-B digests of the last keccak_run; valid until
+ * the next upload/destroy.  EM_ERR_INPUT if the plan has not run. */
+int ethrex_mi355_keccak_device_digests(em_keccak_plan *plan,
+                                       const void **ptr, size_t *n);
 
 int ethrex_mi355_ntt_plan_create(size_t n, em_ntt_plan **plan);
 int ethrex_mi355_ntt_plan_destroy(em_ntt_plan *plan);
@@ -159,6 +163,20 @@ int ethrex_mi355_ntt_last_times(em_ntt_plan *plan, double times_ms[3]);
  * for the on-device MSM handoff (ethrex_mi355_msm_scalars_from_ntt) */
 int ethrex_mi355_ntt_device_data(em_ntt_plan *plan, const void **ptr,
                                  size_t *n);
+/* fill the plan's n resident elements with wrap vector v1 from m device
+ * digests; synchronous; leaves the data in the input buffer (cur = 0).
+ * Wrap vector v1 (DESIGN.md "Wrap vector v1"): R = pairwise keccak256 tree
+ * root of the m digests (odd tail promoted unchanged); block j =
+ * keccak-f1600 of the single padded rate block
+ * domain || R || le64(m) || le64(j) || digest[j mod m]; element 4j+t = the
+ * big-endian integer of state bytes [32t, 32t+32) reduced mod r.
+ * EM_ERR_INPUT for null pointers or m == 0.  d_digests32 is a DEVICE
+ * pointer (ethrex_mi355_keccak_device_digests); domain is a host pointer. */
+int ethrex_mi355_ntt_fill_from_digests(em_ntt_plan *plan,
+                                       const void *d_digests32, size_t m,
+                                       const uint8_t domain[32]);
+/* HIP-event time of the last fill (tree levels + expansion), milliseconds */
+int ethrex_mi355_ntt_last_fill_ms(em_ntt_plan *plan, double *ms);
 
 /* ---- deterministic input generation (host-side; the product restatement
  *      of BASELINE.md's xoshiro256++/splitmix64 scheme; parity-tested
