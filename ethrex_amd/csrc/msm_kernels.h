@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 #include "gpu_field.h"   // fe4: Fr scalar handling
 #include "gpu_g1_9.h"    // fe9: Fq / G1 compute core
+#include "gpu_g1_9_lazy.h"  // BN254 bucket walk: lazy signed mixed add
 #include "gpu_g2.h"      // fp2: BLS12-381 G2 specializations
 
 namespace em {
@@ -299,6 +300,29 @@ k_bucket_acc(const g1aT<C> *__restrict__ pts, const uint32_t *__restrict__ vals,
     // add so the dependent idx->point load chain overlaps the VALU work.
     uint32_t v = GATHER ? vals[lo] : 0;
     g1aT<C> p = GATHER ? pts[v & IMASK] : pts[lo];
+    // BN254 (L=9) gather walks use the lazy signed add: the accumulator
+    // lives under the looser invariant of gpu_g1_9_lazy.h, infinity rides
+    // in a register flag (acc stays g1_inf9() while it is set), and the
+    // bucket is tightened to norm2p once at the end.  BLS (L=14: no lazy
+    // headroom) and the tree finisher keep the g1_add_affine9 loop below.
+    if constexpr (GATHER && C::F::L == 9) {
+        bool acc_inf = true;
+        for (uint32_t t = lo; t < hi; t++) {
+            g1aT<C> cur = p;
+            uint32_t vc = v;
+            uint32_t nxt = t + 1 < hi ? t + 1 : t;
+            v = vals[nxt];
+            p = pts[v & IMASK];
+            if constexpr (CFG::SIGNED) {
+                if (vc & SGN_SKIP) continue;  // parked zero digit / infinity
+            }
+            // sign folded into the add (no negate of cur.y)
+            g1_madd_lazy9<C>(acc, acc_inf, cur,
+                             CFG::SIGNED && (vc & SGN_NEG) != 0);
+        }
+        buckets[b] = g1_lazy_finish9<C>(acc);
+        return;
+    }
     for (uint32_t t = lo; t < hi; t++) {
         g1aT<C> cur = p;
         uint32_t vc = v;
