@@ -20,17 +20,16 @@ using namespace em;
 
 // ============================ NTT plan ============================
 
-struct em_ntt_plan {
-    size_t n;
-    int logn;
+// transform shape + twiddle set of one size: everything a transform needs
+// except the data buffers.  Shared by em_ntt_plan (one vector) and
+// em_quot_plan (three vectors over one twiddle set).
+struct ntt_tw {
+    size_t n = 0;
+    int logn = 0;
     bool fused = false;       // four-step path (13 <= logn <= 24)
     bool fused2 = false;      // two-level four-step (25 <= logn <= 26)
     int logN1 = 0, logN2 = 0;
     int logM1 = 0, logM2 = 0; // inner split of N2 (fused2)
-    int cur = 0;              // which buffer holds the data: 0=d_data 1=d_work
-    fe4 *d_data = nullptr;    // packed 4x64 Montgomery (fe4m), 32 B/elem
-    fe4 *d_work = nullptr;    // fused: transpose ping-pong buffer
-    uint8_t *d_bytes = nullptr;
     fe9 *d_tw = nullptr;      // fallback: forward twiddles, n/2
     fe9 *d_tw_inv = nullptr;
     fe4 *d_twfull = nullptr;      // fused: TW2[c][k] = w^(k*c), streamed
@@ -46,6 +45,25 @@ struct em_ntt_plan {
     fe9 *d_twrowB = nullptr;      // fused2: inner M2/2 (+inv)
     fe9 *d_twrowB_inv = nullptr;
     fe9 *d_ninv = nullptr;        // 1/n (fe9 Montgomery)
+    // coset tables (built on first coset use, ntt_tw_coset_init).  Index
+    // split i = hi * 2^lo_bits + lo with cs_logA high bits / cs_logB low
+    // bits forward and the reverse inverse — (logN1, logN2) on the
+    // four-step path, so the row kernels can use them per row / element:
+    //   cs_f_hi[r] = (g^(2^logB))^r      2^logA entries
+    //   cs_f_lo[c] = g^c                 2^logB entries
+    //   cs_i_hi[k2] = (g^-(2^logA))^k2   2^logB entries
+    //   cs_i_lo[k1] = g^-k1 / n          2^logA entries
+    bool coset_ok = false;
+    int cs_logA = 0, cs_logB = 0;
+    fe9 *cs_f_hi = nullptr, *cs_f_lo = nullptr;
+    fe9 *cs_i_hi = nullptr, *cs_i_lo = nullptr;
+};
+
+struct em_ntt_plan : ntt_tw {
+    int cur = 0;              // which buffer holds the data: 0=d_data 1=d_work
+    fe4 *d_data = nullptr;    // packed 4x64 Montgomery (fe4m), 32 B/elem
+    fe4 *d_work = nullptr;    // fused: transpose ping-pong buffer
+    uint8_t *d_bytes = nullptr;
     uint32_t *d_err = nullptr;
     hipEvent_t ev[4];
     double last_ms[3] = {0, 0, 0};
@@ -99,6 +117,54 @@ static void launch_row(uint32_t nrows, int logM, fe4 *data,
     }
 }
 
+// the same dispatch for the coset instantiations (COSET = 1: P1 of the
+// forward transform, 2: P2 of the inverse; see ntt_kernels.h)
+template <int COSET>
+static void launch_row_coset(uint32_t nrows, int logM, fe4 *data,
+                             const fe9 *tw_row, const fe4 *tw2,
+                             const fe9 *cs_elem, const fe9 *cs_row) {
+    size_t lds = (((size_t)1 << logM) + (((size_t)1 << logM) >> 6)) *
+                 sizeof(fe9);
+    static int r4 = std::getenv("EM_NTT_R8") ? 0 : 1;
+    static int td = std::getenv("EM_NTT_TD") ? atoi(std::getenv("EM_NTT_TD"))
+                                             : 1024;
+    if (r4) {
+        hipLaunchKernelGGL(k_ntt_row4_coset<COSET>, dim3(nrows), dim3(td),
+                           lds, 0, data, logM, tw_row, tw2, cs_elem, cs_row);
+    } else {
+        hipLaunchKernelGGL(k_ntt_row_coset<COSET>, dim3(nrows), dim3(512),
+                           lds, 0, data, logM, tw_row, tw2, cs_elem, cs_row);
+    }
+}
+
+// out[j] = s * base^j, j < count (the coset tables)
+static int gen_pow_table(fe9 *d_out, size_t count, fe9 base, fe9 s) {
+    fe9 b2k[32];
+    b2k[0] = base;
+    for (int k = 1; k < 32; k++) b2k[k] = mont_sqr9<Fr9T>(b2k[k - 1]);
+    fe9 *d_b2k;
+    HIP_TRY(hipMalloc(&d_b2k, sizeof(b2k)));
+    HIP_TRY(hipMemcpy(d_b2k, b2k, sizeof(b2k), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_gen_pow, dim3(blocks_for(count, 256)), dim3(256), 0,
+                       0, d_out, count, d_b2k, 32, s);
+    HIP_TRY(hipDeviceSynchronize());
+    (void)hipFree(d_b2k);
+    return EM_OK;
+}
+
+// the coset generator g = 5 (Montgomery), the multiplicative generator of
+// Fr that gnark-crypto and arkworks use for BN254
+static fe9 coset_gen() {
+    fe9 five = fe9_zero();
+    five.v[0] = 5;
+    return to_mont9<Fr9T>(five);
+}
+
+static fe9 sqr_times(fe9 x, int k) {
+    for (int i = 0; i < k; i++) x = mont_sqr9<Fr9T>(x);
+    return x;
+}
+
 // reordered streamed table TW2[c*M + k] = w^(k*c) (fe4m), c < rows:
 // P1's per-row twiddle read becomes a coalesced stream instead of a
 // stride-c gather over an n-sized table (a full cache line per element).
@@ -121,14 +187,13 @@ static int gen_tw2_table(fe4 *d_out, uint32_t M, size_t rows, bool inverse,
     return EM_OK;
 }
 
-extern "C" int ethrex_mi355_ntt_plan_create(size_t n, em_ntt_plan **plan) {
-    if (!plan || n == 0 || (n & (n - 1))) return EM_ERR_INPUT;
+static void ntt_tw_free(ntt_tw *p);
+
+// n a power of two <= 2^28 (checked by the callers); on failure the
+// caller frees what was allocated (ntt_tw_free)
+static int ntt_tw_create(ntt_tw *p, size_t n) {
     int logn = 0;
     while (((size_t)1 << logn) < n) logn++;
-    if (logn > bn254::FR_TWO_ADICITY) return EM_ERR_INPUT;
-    int rc = require_gpu();
-    if (rc) return rc;
-    em_ntt_plan *p = new em_ntt_plan();
     p->n = n;
     p->logn = logn;
     // one-level four-step up to 2^24 (A/B-measured best: 3.37 ms vs 3.76
@@ -146,9 +211,6 @@ extern "C" int ethrex_mi355_ntt_plan_create(size_t n, em_ntt_plan **plan) {
     auto mal = [&](void **ptr, size_t bytes) {
         if (e == hipSuccess) e = hipMalloc(ptr, bytes);
     };
-    mal((void **)&p->d_data, n * sizeof(fe4));
-    mal((void **)&p->d_bytes, n * 32);
-    mal((void **)&p->d_err, 4);
     if (p->fused || p->fused2) {
         if (p->fused) {
             p->logN1 = (logn + 1) / 2;
@@ -168,7 +230,6 @@ extern "C" int ethrex_mi355_ntt_plan_create(size_t n, em_ntt_plan **plan) {
             p->logM1 = (p->logN2 + 1) / 2;
             p->logM2 = p->logN2 / 2;
         }
-        mal((void **)&p->d_work, n * sizeof(fe4));
         mal((void **)&p->d_twfull, n * sizeof(fe4));
         mal((void **)&p->d_twfull_inv, n * sizeof(fe4));
         mal((void **)&p->d_twrow1, ((size_t)1 << (p->logN1 - 1)) * sizeof(fe9));
@@ -206,11 +267,7 @@ extern "C" int ethrex_mi355_ntt_plan_create(size_t n, em_ntt_plan **plan) {
             (const void *)&k_ntt_row4,
             hipFuncAttributeMaxDynamicSharedMemorySize,
             (int)((4096 + 64) * sizeof(fe9)));
-    for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipEventCreate(&p->ev[i]);
-    if (e != hipSuccess) {
-        ethrex_mi355_ntt_plan_destroy(p);
-        return hip_fail(e, "ntt_plan_create");
-    }
+    if (e != hipSuccess) return hip_fail(e, "ntt_plan_create");
     if (p->fused || p->fused2) {
         int rc2;
         uint32_t N1g = 1u << p->logN1;
@@ -253,15 +310,92 @@ extern "C" int ethrex_mi355_ntt_plan_create(size_t n, em_ntt_plan **plan) {
         if ((rc2 = gen_tw_table(p->d_tw_inv, half, logn ? logn : 1, true, logn)))
             return rc2;
     }
+    return EM_OK;
+}
+
+// coset tables + the coset kernels' LDS opt-in, on first coset use
+static int ntt_tw_coset_init(ntt_tw *p) {
+    if (p->coset_ok) return EM_OK;
+    if (p->fused) {
+        p->cs_logA = p->logN1;
+        p->cs_logB = p->logN2;
+    } else {
+        p->cs_logA = (p->logn + 1) / 2;
+        p->cs_logB = p->logn / 2;
+    }
+    size_t nA = (size_t)1 << p->cs_logA, nB = (size_t)1 << p->cs_logB;
+    if (!p->cs_f_hi) HIP_TRY(hipMalloc((void **)&p->cs_f_hi, nA * sizeof(fe9)));
+    if (!p->cs_f_lo) HIP_TRY(hipMalloc((void **)&p->cs_f_lo, nB * sizeof(fe9)));
+    if (!p->cs_i_hi) HIP_TRY(hipMalloc((void **)&p->cs_i_hi, nB * sizeof(fe9)));
+    if (!p->cs_i_lo) HIP_TRY(hipMalloc((void **)&p->cs_i_lo, nA * sizeof(fe9)));
+    HIP_TRY(hipFuncSetAttribute(
+        (const void *)&k_ntt_row_coset<1>,
+        hipFuncAttributeMaxDynamicSharedMemorySize,
+        (int)((4096 + 64) * sizeof(fe9))));
+    HIP_TRY(hipFuncSetAttribute(
+        (const void *)&k_ntt_row_coset<2>,
+        hipFuncAttributeMaxDynamicSharedMemorySize,
+        (int)((4096 + 64) * sizeof(fe9))));
+    HIP_TRY(hipFuncSetAttribute(
+        (const void *)&k_ntt_row4_coset<1>,
+        hipFuncAttributeMaxDynamicSharedMemorySize,
+        (int)((4096 + 64) * sizeof(fe9))));
+    HIP_TRY(hipFuncSetAttribute(
+        (const void *)&k_ntt_row4_coset<2>,
+        hipFuncAttributeMaxDynamicSharedMemorySize,
+        (int)((4096 + 64) * sizeof(fe9))));
+    fe9 one = fe9_load(bn254::FR9_ONE);
+    fe9 g = coset_gen();
+    fe9 ginv = mont_inv9<Fr9T>(g);
+    fe9 ninv = fe9_load(bn254::FR9_INV_POW2[p->logn]);
+    int rc;
+    if ((rc = gen_pow_table(p->cs_f_hi, nA, sqr_times(g, p->cs_logB), one)))
+        return rc;
+    if ((rc = gen_pow_table(p->cs_f_lo, nB, g, one))) return rc;
+    if ((rc = gen_pow_table(p->cs_i_hi, nB, sqr_times(ginv, p->cs_logA), one)))
+        return rc;
+    if ((rc = gen_pow_table(p->cs_i_lo, nA, ginv, ninv))) return rc;
+    p->coset_ok = true;
+    return EM_OK;
+}
+
+static bool ntt_size_ok(size_t n) {
+    return n != 0 && !(n & (n - 1)) &&
+           n <= ((size_t)1 << bn254::FR_TWO_ADICITY);
+}
+
+extern "C" int ethrex_mi355_ntt_plan_create(size_t n, em_ntt_plan **plan) {
+    if (!plan || !ntt_size_ok(n)) return EM_ERR_INPUT;
+    int rc = require_gpu();
+    if (rc) return rc;
+    em_ntt_plan *p = new em_ntt_plan();
+    rc = ntt_tw_create(p, n);
+    hipError_t e = hipSuccess;
+    auto mal = [&](void **ptr, size_t bytes) {
+        if (e == hipSuccess) e = hipMalloc(ptr, bytes);
+    };
+    if (!rc) {
+        mal((void **)&p->d_data, n * sizeof(fe4));
+        mal((void **)&p->d_bytes, n * 32);
+        mal((void **)&p->d_err, 4);
+        if (p->fused || p->fused2) mal((void **)&p->d_work, n * sizeof(fe4));
+        for (int i = 0; i < 4 && e == hipSuccess; i++)
+            e = hipEventCreate(&p->ev[i]);
+        if (e != hipSuccess) rc = hip_fail(e, "ntt_plan_create");
+    }
+    if (rc) {
+        ethrex_mi355_ntt_plan_destroy(p);
+        return rc;
+    }
     *plan = p;
     return EM_OK;
 }
 
-extern "C" int ethrex_mi355_ntt_plan_destroy(em_ntt_plan *p) {
-    if (!p) return EM_ERR_INPUT;
-    (void)hipFree(p->d_data);
-    (void)hipFree(p->d_work);
-    (void)hipFree(p->d_bytes);
+static void ntt_tw_free(ntt_tw *p) {
+    (void)hipFree(p->cs_f_hi);
+    (void)hipFree(p->cs_f_lo);
+    (void)hipFree(p->cs_i_hi);
+    (void)hipFree(p->cs_i_lo);
     (void)hipFree(p->d_tw);
     (void)hipFree(p->d_tw_inv);
     (void)hipFree(p->d_twfull);
@@ -277,6 +411,14 @@ extern "C" int ethrex_mi355_ntt_plan_destroy(em_ntt_plan *p) {
     (void)hipFree(p->d_twrow2);
     (void)hipFree(p->d_twrow2_inv);
     (void)hipFree(p->d_ninv);
+}
+
+extern "C" int ethrex_mi355_ntt_plan_destroy(em_ntt_plan *p) {
+    if (!p) return EM_ERR_INPUT;
+    ntt_tw_free(p);
+    (void)hipFree(p->d_data);
+    (void)hipFree(p->d_work);
+    (void)hipFree(p->d_bytes);
     (void)hipFree(p->d_err);
     (void)hipFree(p->d_tree);
     if (p->ev_fill_ok) {
@@ -357,35 +499,57 @@ extern "C" int ethrex_mi355_ntt_last_fill_ms(em_ntt_plan *p, double *ms) {
     return EM_OK;
 }
 
-extern "C" int ethrex_mi355_ntt_run(em_ntt_plan *p, int inverse) {
-    if (!p) return EM_ERR_INPUT;
+// Enqueue one transform of `cur` on the null stream (no sync).  `oth` is
+// the transpose ping-pong buffer of the four-step paths (unused, may be
+// null, on the stage-by-stage path); *flipped tells whether the result is
+// in `oth`.  ev_mid, when given, is recorded after the first pass (the
+// [0]/[1] split of ntt_last_times).  coset: 0 plain; 1 the coset transform
+// of that direction — fused into P1 (forward) / P2 (inverse) on the
+// four-step path, the standalone k_coset_scale pass elsewhere and under
+// EM_NTT_COSET_UNFUSED.  The coset inverse takes its 1/n from the coset
+// tables, so the transform's own 1/n is skipped.  With coset = 0 the launch
+// sequence is what ethrex_mi355_ntt_run has always issued.
+static int ntt_exec(const ntt_tw *p, fe4 *cur, fe4 *oth, int inverse,
+                    int coset, hipEvent_t *ev_mid, bool *flipped) {
     size_t n = p->n;
-    fe4 *cur = p->cur ? p->d_work : p->d_data;
-    fe4 *oth = p->cur ? p->d_data : p->d_work;
-    HIP_TRY(hipEventRecord(p->ev[0], 0));
+    static int unfused = std::getenv("EM_NTT_COSET_UNFUSED") ? 1 : 0;
+    const bool cs_fused = coset && p->fused && !unfused;
+    const bool cs_pass = coset && !cs_fused;   // standalone scale pass
+    const fe9 *ninv = (inverse && !coset) ? p->d_ninv : (const fe9 *)nullptr;
+    *flipped = false;
+    if (cs_pass && !inverse)
+        hipLaunchKernelGGL(k_coset_scale, dim3(blocks_for(n, 256)), dim3(256),
+                           0, 0, cur, n, p->cs_f_hi, p->cs_f_lo, p->cs_logB);
     if (p->fused) {
         uint32_t N1 = 1u << p->logN1, N2 = 1u << p->logN2;
         // T0: A[r][c] -> A1[c][r]
         hipLaunchKernelGGL(k_transpose_fe4, dim3(N2 / 32, N1 / 32), dim3(256), 0,
                            0, cur, oth, N1, N2);
-        HIP_TRY(hipEventRecord(p->ev[1], 0));
+        if (ev_mid) HIP_TRY(hipEventRecord(*ev_mid, 0));
         // P1: row NTT_N1 over each of the N2 rows + w^(k1*c) twiddle
-        launch_row(N2, p->logN1,
-                   oth, inverse ? p->d_twrow1_inv : p->d_twrow1,
-                   inverse ? p->d_twfull_inv : p->d_twfull,
-                   (const fe9 *)nullptr);
+        if (cs_fused && !inverse)
+            launch_row_coset<1>(N2, p->logN1, oth, p->d_twrow1, p->d_twfull,
+                                p->cs_f_hi, p->cs_f_lo);
+        else
+            launch_row(N2, p->logN1,
+                       oth, inverse ? p->d_twrow1_inv : p->d_twrow1,
+                       inverse ? p->d_twfull_inv : p->d_twfull,
+                       (const fe9 *)nullptr);
         // T1
         hipLaunchKernelGGL(k_transpose_fe4, dim3(N1 / 32, N2 / 32), dim3(256), 0,
                            0, oth, cur, N2, N1);
         // P2: row NTT_N2 (+ 1/n scale on iNTT)
-        launch_row(N1, p->logN2,
-                   cur, inverse ? p->d_twrow2_inv : p->d_twrow2,
-                   (const fe4 *)nullptr,
-                   inverse ? p->d_ninv : (const fe9 *)nullptr);
+        if (cs_fused && inverse)
+            launch_row_coset<2>(N1, p->logN2, cur, p->d_twrow2_inv,
+                                (const fe4 *)nullptr, p->cs_i_hi, p->cs_i_lo);
+        else
+            launch_row(N1, p->logN2,
+                       cur, inverse ? p->d_twrow2_inv : p->d_twrow2,
+                       (const fe4 *)nullptr, ninv);
         // T2: natural order
         hipLaunchKernelGGL(k_transpose_fe4, dim3(N2 / 32, N1 / 32), dim3(256), 0,
                            0, cur, oth, N1, N2);
-        p->cur ^= 1;
+        *flipped = true;
     } else if (p->fused2) {
         // two-level four-step (25 <= logn <= 26): the outer P2 row length
         // (2^13/2^14) exceeds the 4096-element LDS row kernel, so each of
@@ -403,7 +567,7 @@ extern "C" int ethrex_mi355_ntt_run(em_ntt_plan *p, int inverse) {
         // T0 + P1 + T1: outer column NTTs (length N1) + w_n^(k1 c)
         hipLaunchKernelGGL(k_transpose_fe4, dim3(N2 / 32, N1 / 32), dim3(256),
                            0, 0, cur, oth, N1, N2);
-        HIP_TRY(hipEventRecord(p->ev[1], 0));
+        if (ev_mid) HIP_TRY(hipEventRecord(*ev_mid, 0));
         if (p->logN1 <= 10) {
             hipLaunchKernelGGL(k_ntt_row_small, dim3(N2 * N1 / 1024),
                                dim3(512), 0, 0, oth, p->logN1, tr1, tf,
@@ -424,8 +588,7 @@ extern "C" int ethrex_mi355_ntt_run(em_ntt_plan *p, int inverse) {
         hipLaunchKernelGGL(k_ntt_row_small, dim3(N1 * M1 * M2 / 1024),
                            dim3(512), 0, 0, cur, p->logM2, trB,
                            (const fe4 *)nullptr,
-                           inverse ? p->d_ninv : (const fe9 *)nullptr,
-                           0xffffffffu);
+                           ninv, 0xffffffffu);
         hipLaunchKernelGGL(k_transpose_fe4, dim3(M2 / 32, M1 / 32, N1),
                            dim3(256), 0, 0, cur, oth, M1, M2);
         // outer T2 -> natural order
@@ -437,17 +600,32 @@ extern "C" int ethrex_mi355_ntt_run(em_ntt_plan *p, int inverse) {
             hipLaunchKernelGGL(k_bit_reverse, dim3(blocks_for(n, 256)), dim3(256),
                                0, 0, cur, n, p->logn);
         }
-        HIP_TRY(hipEventRecord(p->ev[1], 0));
+        if (ev_mid) HIP_TRY(hipEventRecord(*ev_mid, 0));
         const fe9 *tw = inverse ? p->d_tw_inv : p->d_tw;
         for (int s = 1; s <= p->logn; s++) {
             hipLaunchKernelGGL(k_ntt_stage, dim3(blocks_for(n / 2, 256)),
                                dim3(256), 0, 0, cur, tw, n, p->logn, s);
         }
-        if (inverse) {
+        if (inverse && !coset) {
             hipLaunchKernelGGL(k_ntt_scale, dim3(blocks_for(n, 256)), dim3(256),
                                0, 0, cur, n, p->logn);
         }
     }
+    if (cs_pass && inverse)
+        hipLaunchKernelGGL(k_coset_scale, dim3(blocks_for(n, 256)), dim3(256),
+                           0, 0, *flipped ? oth : cur, n, p->cs_i_hi,
+                           p->cs_i_lo, p->cs_logA);
+    return EM_OK;
+}
+
+static int ntt_plan_run(em_ntt_plan *p, int inverse, int coset) {
+    fe4 *cur = p->cur ? p->d_work : p->d_data;
+    fe4 *oth = p->cur ? p->d_data : p->d_work;
+    HIP_TRY(hipEventRecord(p->ev[0], 0));
+    bool flipped;
+    int rc = ntt_exec(p, cur, oth, inverse, coset, &p->ev[1], &flipped);
+    if (rc) return rc;
+    if (flipped) p->cur ^= 1;
     HIP_TRY(hipEventRecord(p->ev[2], 0));
     HIP_TRY(hipDeviceSynchronize());
     float ms;
@@ -458,6 +636,20 @@ extern "C" int ethrex_mi355_ntt_run(em_ntt_plan *p, int inverse) {
     HIP_TRY(hipEventElapsedTime(&ms, p->ev[0], p->ev[2]));
     p->last_ms[2] = ms;
     return EM_OK;
+}
+
+extern "C" int ethrex_mi355_ntt_run(em_ntt_plan *p, int inverse) {
+    if (!p) return EM_ERR_INPUT;
+    return ntt_plan_run(p, inverse, 0);
+}
+
+// coset transform (g = 5): forward = NTT of a_i g^i, inverse = iNTT then
+// g^-i; same buffer rules as ntt_run
+extern "C" int ethrex_mi355_ntt_run_coset(em_ntt_plan *p, int inverse) {
+    if (!p) return EM_ERR_INPUT;
+    int rc = ntt_tw_coset_init(p);
+    if (rc) return rc;
+    return ntt_plan_run(p, inverse, 1);
 }
 
 extern "C" int ethrex_mi355_ntt_download(em_ntt_plan *p, uint8_t *elems32) {
@@ -498,5 +690,195 @@ extern "C" int ethrex_mi355_ntt_device_data(em_ntt_plan *p, const void **ptr,
     if (!p || !ptr) return EM_ERR_INPUT;
     *ptr = p->cur ? p->d_work : p->d_data;
     if (n) *n = p->n;
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_bn254_fr_coset_ntt(uint8_t *elems32, size_t n,
+                                               int inverse) {
+    if (!elems32 || n == 0) return EM_ERR_INPUT;
+    em_ntt_plan *p = nullptr;
+    int rc = ethrex_mi355_ntt_plan_create(n, &p);
+    if (rc) return rc;
+    rc = ethrex_mi355_ntt_upload(p, elems32);
+    if (!rc) rc = ethrex_mi355_ntt_run_coset(p, inverse);
+    if (!rc) rc = ethrex_mi355_ntt_download(p, elems32);
+    ethrex_mi355_ntt_plan_destroy(p);
+    return rc;
+}
+
+// ===================== quotient polynomial (Groth16 H) =====================
+// h = coset_inv((coset_fwd(intt(a)) . coset_fwd(intt(b)) - coset_fwd(intt(c)))
+//               * (g^n - 1)^-1)   (DESIGN.md "Quotient polynomial").
+// One twiddle set, three resident vectors and one work buffer: the four
+// buffers rotate — a four-step transform leaves its result in the work
+// buffer, which then becomes that slot, and the slot's old buffer becomes
+// the work buffer.  The work buffer doubles as the byte staging area of
+// upload/download (n * 32 bytes either way).
+
+struct em_quot_plan {
+    ntt_tw tw;
+    fe4 *buf[4] = {nullptr, nullptr, nullptr, nullptr};
+    int slot[3] = {0, 1, 2};  // buf index of a, b, c
+    int work = 3;             // buf index of the work buffer
+    bool loaded[3] = {false, false, false};
+    bool has_h = false;       // h sits in slot a
+    uint32_t *d_err = nullptr;
+    fe9 dconst;               // (g^n - 1)^-1, Montgomery
+    hipEvent_t ev[5];
+    int n_ev = 0;
+    double last_ms[5] = {0, 0, 0, 0, 0};
+};
+
+extern "C" int ethrex_mi355_quot_plan_create(size_t n, em_quot_plan **plan) {
+    if (!plan || !ntt_size_ok(n)) return EM_ERR_INPUT;
+    int rc = require_gpu();
+    if (rc) return rc;
+    em_quot_plan *q = new em_quot_plan();
+    rc = ntt_tw_create(&q->tw, n);
+    if (!rc) rc = ntt_tw_coset_init(&q->tw);
+    if (!rc) {
+        hipError_t e = hipSuccess;
+        for (int i = 0; i < 4 && e == hipSuccess; i++)
+            e = hipMalloc((void **)&q->buf[i], n * sizeof(fe4));
+        if (e == hipSuccess) e = hipMalloc((void **)&q->d_err, 4);
+        for (; q->n_ev < 5 && e == hipSuccess; q->n_ev++)
+            e = hipEventCreate(&q->ev[q->n_ev]);
+        if (e != hipSuccess) {
+            if (q->n_ev) q->n_ev--;   // the failed slot holds no event
+            rc = hip_fail(e, "quot_plan_create");
+        }
+    }
+    if (rc) {
+        ethrex_mi355_quot_plan_destroy(q);
+        return rc;
+    }
+    // d = (g^n - 1)^-1; g^n != 1 for every n <= 2^28 (g generates Fr*)
+    fe9 gn = sqr_times(coset_gen(), q->tw.logn);
+    q->dconst = mont_inv9<Fr9T>(subn9<Fr9T>(gn, fe9_load(bn254::FR9_ONE)));
+    *plan = q;
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_quot_plan_destroy(em_quot_plan *q) {
+    if (!q) return EM_ERR_INPUT;
+    ntt_tw_free(&q->tw);
+    for (int i = 0; i < 4; i++) (void)hipFree(q->buf[i]);
+    (void)hipFree(q->d_err);
+    for (int i = 0; i < q->n_ev; i++) (void)hipEventDestroy(q->ev[i]);
+    delete q;
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_quot_upload(em_quot_plan *q, int which,
+                                        const uint8_t *elems32) {
+    if (!q || !elems32 || which < 0 || which > 2) return EM_ERR_INPUT;
+    size_t n = q->tw.n;
+    uint8_t *stage = (uint8_t *)q->buf[q->work];
+    q->loaded[which] = false;
+    if (which == 0) q->has_h = false;
+    HIP_TRY(hipMemset(q->d_err, 0, 4));
+    HIP_TRY(hipMemcpy(stage, elems32, n * 32, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_fr_from_be, dim3(blocks_for(n, 256)), dim3(256), 0, 0,
+                       stage, q->buf[q->slot[which]], n, q->d_err);
+    uint32_t err;
+    HIP_TRY(hipMemcpy(&err, q->d_err, 4, hipMemcpyDeviceToHost));
+    if (err) return EM_ERR_INPUT;
+    q->loaded[which] = true;
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_quot_load_device(em_quot_plan *q, int which,
+                                             const void *d_fe4m) {
+    if (!q || !d_fe4m || which < 0 || which > 2) return EM_ERR_INPUT;
+    q->loaded[which] = false;
+    if (which == 0) q->has_h = false;
+    HIP_TRY(hipMemcpy(q->buf[q->slot[which]], d_fe4m,
+                      q->tw.n * sizeof(fe4), hipMemcpyDeviceToDevice));
+    q->loaded[which] = true;
+    return EM_OK;
+}
+
+// c = a (.) b; needs a and b loaded
+extern "C" int ethrex_mi355_quot_mul_ab_into_c(em_quot_plan *q) {
+    if (!q || !q->loaded[0] || !q->loaded[1]) return EM_ERR_INPUT;
+    size_t n = q->tw.n;
+    hipLaunchKernelGGL(k_fr_mul, dim3(blocks_for(n, 256)), dim3(256), 0, 0,
+                       q->buf[q->slot[0]], q->buf[q->slot[1]],
+                       q->buf[q->slot[2]], n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    q->loaded[2] = true;
+    return EM_OK;
+}
+
+// one transform of slot `which`, rotating the buffers if it flipped
+static int quot_exec(em_quot_plan *q, int which, int inverse, int coset) {
+    bool flipped;
+    int rc = ntt_exec(&q->tw, q->buf[q->slot[which]], q->buf[q->work],
+                      inverse, coset, nullptr, &flipped);
+    if (rc) return rc;
+    if (flipped) {
+        int t = q->slot[which];
+        q->slot[which] = q->work;
+        q->work = t;
+    }
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_quot_run(em_quot_plan *q) {
+    if (!q || !q->loaded[0] || !q->loaded[1] || !q->loaded[2])
+        return EM_ERR_INPUT;
+    size_t n = q->tw.n;
+    int rc;
+    q->loaded[0] = q->loaded[1] = q->loaded[2] = false;
+    q->has_h = false;
+    HIP_TRY(hipEventRecord(q->ev[0], 0));
+    for (int v = 0; v < 3; v++)
+        if ((rc = quot_exec(q, v, 1, 0))) return rc;
+    HIP_TRY(hipEventRecord(q->ev[1], 0));
+    for (int v = 0; v < 3; v++)
+        if ((rc = quot_exec(q, v, 0, 1))) return rc;
+    HIP_TRY(hipEventRecord(q->ev[2], 0));
+    hipLaunchKernelGGL(k_quot_pointwise, dim3(blocks_for(n, 256)), dim3(256),
+                       0, 0, q->buf[q->slot[0]], q->buf[q->slot[1]],
+                       q->buf[q->slot[2]], n, q->dconst);
+    HIP_TRY(hipEventRecord(q->ev[3], 0));
+    if ((rc = quot_exec(q, 0, 1, 1))) return rc;
+    HIP_TRY(hipEventRecord(q->ev[4], 0));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    float ms;
+    for (int i = 0; i < 4; i++) {
+        HIP_TRY(hipEventElapsedTime(&ms, q->ev[i], q->ev[i + 1]));
+        q->last_ms[i] = ms;
+    }
+    HIP_TRY(hipEventElapsedTime(&ms, q->ev[0], q->ev[4]));
+    q->last_ms[4] = ms;
+    q->has_h = true;
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_quot_download(em_quot_plan *q, uint8_t *elems32) {
+    if (!q || !elems32 || !q->has_h) return EM_ERR_INPUT;
+    size_t n = q->tw.n;
+    uint8_t *stage = (uint8_t *)q->buf[q->work];
+    hipLaunchKernelGGL(k_fr_to_be, dim3(blocks_for(n, 256)), dim3(256), 0, 0,
+                       q->buf[q->slot[0]], stage, n);
+    HIP_TRY(hipMemcpy(elems32, stage, n * 32, hipMemcpyDeviceToHost));
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_quot_device_data(em_quot_plan *q, const void **ptr,
+                                             size_t *n) {
+    if (!q || !ptr || !q->has_h) return EM_ERR_INPUT;
+    *ptr = q->buf[q->slot[0]];
+    if (n) *n = q->tw.n;
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_quot_last_times(em_quot_plan *q,
+                                            double times_ms[5]) {
+    if (!q || !times_ms) return EM_ERR_INPUT;
+    memcpy(times_ms, q->last_ms, sizeof q->last_ms);
     return EM_OK;
 }

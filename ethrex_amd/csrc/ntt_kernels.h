@@ -168,10 +168,20 @@ k_transpose_fe4(const fe4 *__restrict__ src, fe4 *__restrict__ dst,
 // = a 64-way conflict); with the skew, lane l's slot moves by
 // rev6(l)*65 -> 9*rev6(l) mod 64, a permutation of the banks.
 #define EM_SK(i) ((i) + ((i) >> 6))
-__global__ void __launch_bounds__(512)
-k_ntt_row(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
-          const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
-          uint32_t cmask = 0xffffffffu) {
+// COSET (compile-time; the row kernels' bodies are shared templates so the
+// plain COSET = 0 kernels compile to the code they were before):
+//   0  plain transform; cs_elem / cs_row unused.
+//   1  coset forward, P1: element i is multiplied by cs_elem[i] = (g^N2)^i
+//      on load and output row c additionally by cs_row[c] = g^c.
+//   2  coset inverse, P2: output k of row k1 is multiplied by
+//      cs_row[k1] = g^(-k1) n^-1 and cs_elem[k] = (g^(-N1))^k (scale unused).
+// Both tables are fe9, at most 4096 entries, shared by all rows.
+template <int COSET>
+__device__ __forceinline__ void
+ntt_row_body(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
+             const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
+             uint32_t cmask, const fe9 *__restrict__ cs_elem,
+             const fe9 *__restrict__ cs_row) {
     // dynamic LDS, (M + M/64) fe9 slots: 2048-element rows then run 2
     // blocks/CU (73 KiB) instead of being pinned at the 4096-row footprint
     extern __shared__ fe9 smem[];
@@ -179,7 +189,10 @@ k_ntt_row(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
     fe4 *row = data + (size_t)blockIdx.x * M;
     for (uint32_t i = threadIdx.x; i < M; i += blockDim.x) {
         uint32_t j = __brev(i) >> (32 - logM);
-        smem[EM_SK(j)] = fe4m_unpack(row[i]);
+        if constexpr (COSET == 1)
+            smem[EM_SK(j)] = mont_mul9<Fr9T>(fe4m_unpack(row[i]), cs_elem[i]);
+        else
+            smem[EM_SK(j)] = fe4m_unpack(row[i]);
     }
     __syncthreads();
     int s = 1;
@@ -294,12 +307,43 @@ k_ntt_row(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
     }
     uint64_t c = blockIdx.x & cmask;
     const fe4 *t2row = tw2 ? tw2 + (size_t)c * M : nullptr;
-    for (uint32_t k = threadIdx.x; k < M; k += blockDim.x) {
-        fe9 x = smem[EM_SK(k)];
-        if (t2row) x = mont_mul9<Fr9T>(x, fe4m_unpack(t2row[k]));
-        if (scale) x = mont_mul9<Fr9T>(x, *scale);
-        row[k] = fe4m_pack(x);
+    if constexpr (COSET == 0) {
+        for (uint32_t k = threadIdx.x; k < M; k += blockDim.x) {
+            fe9 x = smem[EM_SK(k)];
+            if (t2row) x = mont_mul9<Fr9T>(x, fe4m_unpack(t2row[k]));
+            if (scale) x = mont_mul9<Fr9T>(x, *scale);
+            row[k] = fe4m_pack(x);
+        }
+    } else {
+        const fe9 rowc = cs_row[c];
+        for (uint32_t k = threadIdx.x; k < M; k += blockDim.x) {
+            fe9 x = mont_mul9<Fr9T>(smem[EM_SK(k)], rowc);
+            if constexpr (COSET == 1)
+                x = mont_mul9<Fr9T>(x, fe4m_unpack(t2row[k]));
+            else
+                x = mont_mul9<Fr9T>(x, cs_elem[k]);
+            row[k] = fe4m_pack(x);
+        }
     }
+}
+
+__global__ void __launch_bounds__(512)
+k_ntt_row(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
+          const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
+          uint32_t cmask = 0xffffffffu) {
+    ntt_row_body<0>(data, logM, tw_row, tw2, scale, cmask, nullptr, nullptr);
+}
+
+// coset instantiations (see COSET above); tw2 is required for COSET = 1
+template <int COSET>
+__global__ void __launch_bounds__(512)
+k_ntt_row_coset(fe4 *__restrict__ data, int logM,
+                const fe9 *__restrict__ tw_row, const fe4 *__restrict__ tw2,
+                const fe9 *__restrict__ cs_elem,
+                const fe9 *__restrict__ cs_row) {
+    static_assert(COSET == 1 || COSET == 2, "coset mode");
+    ntt_row_body<COSET>(data, logM, tw_row, tw2, nullptr, 0xffffffffu, cs_elem,
+                        cs_row);
 }
 
 
@@ -307,16 +351,21 @@ k_ntt_row(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
 // per thread per round trip, launchable at 512/768/1024 threads — more
 // waves/SIMD than the radix-2^3 shape at the cost of 1.5x the LDS round
 // trips.  Same skewed layout and IO as k_ntt_row.
-__global__ void __launch_bounds__(1024)
-k_ntt_row4(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
-           const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
-           uint32_t cmask) {
+template <int COSET>
+__device__ __forceinline__ void
+ntt_row4_body(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
+              const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
+              uint32_t cmask, const fe9 *__restrict__ cs_elem,
+              const fe9 *__restrict__ cs_row) {
     extern __shared__ fe9 smem[];
     const uint32_t M = 1u << logM;
     fe4 *row = data + (size_t)blockIdx.x * M;
     for (uint32_t i = threadIdx.x; i < M; i += blockDim.x) {
         uint32_t j = __brev(i) >> (32 - logM);
-        smem[EM_SK(j)] = fe4m_unpack(row[i]);
+        if constexpr (COSET == 1)
+            smem[EM_SK(j)] = mont_mul9<Fr9T>(fe4m_unpack(row[i]), cs_elem[i]);
+        else
+            smem[EM_SK(j)] = fe4m_unpack(row[i]);
     }
     __syncthreads();
     int s = 1;
@@ -358,12 +407,43 @@ k_ntt_row4(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
     }
     uint64_t c = blockIdx.x & cmask;
     const fe4 *t2row = tw2 ? tw2 + (size_t)c * M : nullptr;
-    for (uint32_t k = threadIdx.x; k < M; k += blockDim.x) {
-        fe9 x = smem[EM_SK(k)];
-        if (t2row) x = mont_mul9<Fr9T>(x, fe4m_unpack(t2row[k]));
-        if (scale) x = mont_mul9<Fr9T>(x, *scale);
-        row[k] = fe4m_pack(x);
+    if constexpr (COSET == 0) {
+        for (uint32_t k = threadIdx.x; k < M; k += blockDim.x) {
+            fe9 x = smem[EM_SK(k)];
+            if (t2row) x = mont_mul9<Fr9T>(x, fe4m_unpack(t2row[k]));
+            if (scale) x = mont_mul9<Fr9T>(x, *scale);
+            row[k] = fe4m_pack(x);
+        }
+    } else {
+        const fe9 rowc = cs_row[c];
+        for (uint32_t k = threadIdx.x; k < M; k += blockDim.x) {
+            fe9 x = mont_mul9<Fr9T>(smem[EM_SK(k)], rowc);
+            if constexpr (COSET == 1)
+                x = mont_mul9<Fr9T>(x, fe4m_unpack(t2row[k]));
+            else
+                x = mont_mul9<Fr9T>(x, cs_elem[k]);
+            row[k] = fe4m_pack(x);
+        }
     }
+}
+
+__global__ void __launch_bounds__(1024)
+k_ntt_row4(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
+           const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
+           uint32_t cmask) {
+    ntt_row4_body<0>(data, logM, tw_row, tw2, scale, cmask, nullptr, nullptr);
+}
+
+// coset instantiations (see COSET above); tw2 is required for COSET = 1
+template <int COSET>
+__global__ void __launch_bounds__(1024)
+k_ntt_row4_coset(fe4 *__restrict__ data, int logM,
+                 const fe9 *__restrict__ tw_row, const fe4 *__restrict__ tw2,
+                 const fe9 *__restrict__ cs_elem,
+                 const fe9 *__restrict__ cs_row) {
+    static_assert(COSET == 1 || COSET == 2, "coset mode");
+    ntt_row4_body<COSET>(data, logM, tw_row, tw2, nullptr, 0xffffffffu, cs_elem,
+                         cs_row);
 }
 
 // packed small-row NTT: 1024/M rows of length M <= 512 per block (the
@@ -413,6 +493,52 @@ __global__ void k_ntt_scale(fe4 *__restrict__ a, size_t n, int logn) {
     if (i >= n) return;
     a[i] = fe4m_pack(mont_mul9<Fr9T>(fe4m_unpack(a[i]),
                                      fe9_load(bn254::FR9_INV_POW2[logn])));
+}
+
+// ---- coset / quotient support (DESIGN.md "Quotient polynomial") ----
+
+// out[j] = s * b^j, j < count (fe9 Montgomery); b2k[k] = b^(2^k), k < bits
+__global__ void k_gen_pow(fe9 *__restrict__ out, size_t count,
+                          const fe9 *__restrict__ b2k, int bits, fe9 s) {
+    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    fe9 acc = s;
+    size_t e = j;
+    for (int k = 0; k < bits && e; k++, e >>= 1)
+        if (e & 1) acc = mont_mul9<Fr9T>(acc, b2k[k]);
+    out[j] = acc;
+}
+
+// standalone coset scale: a[i] *= hi[i >> lo_bits] * lo[i & (2^lo_bits - 1)]
+// (g^(+-i), and the 1/n of the inverse, split over two small tables)
+__global__ void k_coset_scale(fe4 *__restrict__ a, size_t n,
+                              const fe9 *__restrict__ hi,
+                              const fe9 *__restrict__ lo, int lo_bits) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fe9 x = mont_mul9<Fr9T>(fe4m_unpack(a[i]), hi[i >> lo_bits]);
+    x = mont_mul9<Fr9T>(x, lo[i & (((size_t)1 << lo_bits) - 1)]);
+    a[i] = fe4m_pack(x);
+}
+
+// c[i] = a[i] * b[i]
+__global__ void k_fr_mul(const fe4 *__restrict__ a, const fe4 *__restrict__ b,
+                         fe4 *__restrict__ c, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    c[i] = fe4m_pack(mont_mul9<Fr9T>(fe4m_unpack(a[i]), fe4m_unpack(b[i])));
+}
+
+// a[j] = (a[j] * b[j] - c[j]) * d: one pass, reads 3 vectors, writes 1.
+// c is a stored value (norm2p, not a mul output) => subn9.
+__global__ void k_quot_pointwise(fe4 *__restrict__ a,
+                                 const fe4 *__restrict__ b,
+                                 const fe4 *__restrict__ c, size_t n, fe9 d) {
+    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    fe9 ab = mont_mul9<Fr9T>(fe4m_unpack(a[j]), fe4m_unpack(b[j]));
+    fe9 t = subn9<Fr9T>(ab, fe4m_unpack(c[j]));
+    a[j] = fe4m_pack(mont_mul9<Fr9T>(t, d));
 }
 
 }  // namespace em

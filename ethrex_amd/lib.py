@@ -34,7 +34,11 @@ for _f in ("device_count", "set_device", "bn254_g1_add", "bn254_g1_mul",
            "ntt_device_data",
            "ntt_plan_create", "ntt_plan_destroy", "ntt_upload", "ntt_run",
            "ntt_download", "ntt_last_times", "ntt_fill_from_digests",
-           "ntt_last_fill_ms", "keccak_device_digests"):
+           "ntt_last_fill_ms", "keccak_device_digests",
+           "ntt_run_coset", "bn254_fr_coset_ntt", "quot_plan_create",
+           "quot_plan_destroy", "quot_upload", "quot_load_device",
+           "quot_mul_ab_into_c", "quot_run", "quot_download",
+           "quot_device_data", "quot_last_times"):
     getattr(_lib, f"ethrex_mi355_{_f}").restype = ctypes.c_int
 
 
@@ -94,6 +98,15 @@ def fr_ntt(elems: bytes, n: int, inverse: bool):
     buf = _buf(elems)
     rc = _lib.ethrex_mi355_bn254_fr_ntt(buf, ctypes.c_size_t(n),
                                         ctypes.c_int(1 if inverse else 0))
+    return rc, bytes(buf)
+
+
+def coset_ntt(elems: bytes, n: int, inverse: bool):
+    """One-shot coset transform (generator g = 5): forward is the NTT of
+    a_i g^i, inverse the iNTT followed by g^-i."""
+    buf = _buf(elems)
+    rc = _lib.ethrex_mi355_bn254_fr_coset_ntt(
+        buf, ctypes.c_size_t(n), ctypes.c_int(1 if inverse else 0))
     return rc, bytes(buf)
 
 
@@ -204,16 +217,13 @@ class MsmPlan:
         plan's device-resident output at element `offset` (on-device, no
         PCIe; the sp1.rs:122-134 wrap flow feeds the witness NTT output
         into the proving MSM)."""
-        ptr = ctypes.c_void_p()
-        nn = ctypes.c_size_t(0)
-        _check(_lib.ethrex_mi355_ntt_device_data(ntt_plan._p,
-                                                 ctypes.byref(ptr),
-                                                 ctypes.byref(nn)),
-               "ntt_device_data")
-        if offset + self.n > nn.value:
+        # any source with a device_data() -> (ptr, n) accessor: an NttPlan
+        # or a QuotPlan (whose h feeds the Z-basis MSM)
+        ptr, nn = ntt_plan.device_data()
+        if offset + self.n > nn:
             raise HipCoreError(EM_ERR_INPUT,
                                f"scalars_from_ntt: offset {offset} + n "
-                               f"{self.n} exceeds NTT size {nn.value}")
+                               f"{self.n} exceeds NTT size {nn}")
         _check(_lib.ethrex_mi355_msm_scalars_from_ntt(
             self._p, ptr, ctypes.c_uint64(offset)), "msm_scalars_from_ntt")
 
@@ -253,10 +263,24 @@ class NttPlan:
                                          ctypes.c_int(1 if inverse else 0)),
                "ntt_run")
 
+    def run_coset(self, inverse: bool = False):
+        """coset transform (g = 5): forward = NTT of a_i g^i, inverse =
+        iNTT then g^-i; same buffer rules as run()."""
+        _check(_lib.ethrex_mi355_ntt_run_coset(
+            self._p, ctypes.c_int(1 if inverse else 0)), "ntt_run_coset")
+
     def download(self) -> bytes:
         out = (ctypes.c_uint8 * (32 * self.n))()
         _check(_lib.ethrex_mi355_ntt_download(self._p, out), "ntt_download")
         return bytes(out)
+
+    def device_data(self):
+        """(device pointer, n) of the current resident vector (fe4m)"""
+        ptr = ctypes.c_void_p()
+        nn = ctypes.c_size_t(0)
+        _check(_lib.ethrex_mi355_ntt_device_data(
+            self._p, ctypes.byref(ptr), ctypes.byref(nn)), "ntt_device_data")
+        return ptr, nn.value
 
     def last_times(self):
         t = (ctypes.c_double * 3)()
@@ -284,6 +308,79 @@ class NttPlan:
     def destroy(self):
         if self._p:
             _lib.ethrex_mi355_ntt_plan_destroy(self._p)
+            self._p = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class QuotPlan:
+    """Device-resident Groth16 quotient polynomial: three evaluation
+    vectors a, b, c (slots 0, 1, 2) -> h = coset_inv((a~ b~ - c~) /
+    (g^n - 1)), x~ = coset_fwd(intt(x)).  One twiddle set, three vectors
+    and one work buffer; run() consumes the slots."""
+
+    def __init__(self, n: int):
+        self.n = n
+        self._p = ctypes.c_void_p()
+        _check(_lib.ethrex_mi355_quot_plan_create(ctypes.c_size_t(n),
+                                                  ctypes.byref(self._p)),
+               "quot_plan_create")
+
+    def upload(self, which: int, elems: bytes):
+        if len(elems) != 32 * self.n:
+            raise HipCoreError(EM_ERR_INPUT,
+                               f"quot_upload: need {32 * self.n} bytes")
+        _check(_lib.ethrex_mi355_quot_upload(self._p, ctypes.c_int(which),
+                                             _buf(elems)), "quot_upload")
+
+    def load_from_ntt(self, which: int, nplan):
+        """copy the NTT plan's current resident vector into a slot
+        (device to device; after fill_from_digests or a run)"""
+        ptr, nn = nplan.device_data()
+        if nn != self.n:
+            raise HipCoreError(EM_ERR_INPUT,
+                               f"quot_load_from_ntt: size {nn} != {self.n}")
+        _check(_lib.ethrex_mi355_quot_load_device(
+            self._p, ctypes.c_int(which), ptr), "quot_load_device")
+
+    def mul_ab_into_c(self):
+        _check(_lib.ethrex_mi355_quot_mul_ab_into_c(self._p),
+               "quot_mul_ab_into_c")
+
+    def run(self):
+        _check(_lib.ethrex_mi355_quot_run(self._p), "quot_run")
+
+    def download(self) -> bytes:
+        out = (ctypes.c_uint8 * (32 * self.n))()
+        _check(_lib.ethrex_mi355_quot_download(self._p, out),
+               "quot_download")
+        return bytes(out)
+
+    def device_data(self):
+        """(device pointer, n) of h (fe4m); valid until the next
+        load/run/destroy — the MsmPlan.scalars_from_ntt source"""
+        ptr = ctypes.c_void_p()
+        nn = ctypes.c_size_t(0)
+        _check(_lib.ethrex_mi355_quot_device_data(
+            self._p, ctypes.byref(ptr), ctypes.byref(nn)),
+            "quot_device_data")
+        return ptr, nn.value
+
+    def last_times(self):
+        t = (ctypes.c_double * 5)()
+        _check(_lib.ethrex_mi355_quot_last_times(self._p, t),
+               "quot_last_times")
+        return {"intt3_ms": t[0], "coset_ntt3_ms": t[1],
+                "pointwise_ms": t[2], "coset_intt_ms": t[3],
+                "total_ms": t[4]}
+
+    def destroy(self):
+        if self._p:
+            _lib.ethrex_mi355_quot_plan_destroy(self._p)
             self._p = ctypes.c_void_p()
 
     def __del__(self):

@@ -99,8 +99,10 @@ class Mi355Backend:
     core's composition output, carried through the §8f row-3 wire)."""
 
     BINDINGS = ("seed", "witness")
+    COMPOSITIONS = ("direct", "quotient")
 
-    def __init__(self, msm_log2=16, ntt_log2=12, device=0, binding="seed"):
+    def __init__(self, msm_log2=16, ntt_log2=12, device=0, binding="seed",
+                 composition="direct"):
         # binding: how the composition's input vector is derived.
         #   "seed"    — gen_fr over the first 8 bytes of the statement
         #               commitment (host-generated, uploaded);
@@ -111,10 +113,20 @@ class Mi355Backend:
         if binding not in self.BINDINGS:
             raise BackendError(f"mi355: unknown binding {binding!r} "
                                f"(expected one of {self.BINDINGS})")
+        # composition: what feeds the proving MSM.
+        #   "direct"   — the forward NTT of the input vector;
+        #   "quotient" — the Groth16 data flow: two input vectors a, b,
+        #                c = a (.) b on device, and the quotient polynomial
+        #                h = (A*B - C) / (X^n - 1) (QuotPlan; DESIGN.md
+        #                "Quotient polynomial") is the MSM's scalar vector.
+        if composition not in self.COMPOSITIONS:
+            raise BackendError(f"mi355: unknown composition {composition!r} "
+                               f"(expected one of {self.COMPOSITIONS})")
         self.msm_log2 = msm_log2
         self.ntt_log2 = ntt_log2
         self.device = device
         self.binding = binding
+        self.composition = composition
 
     def prover_type(self) -> str:
         # reuses Exec semantics for coordinator keying (no on-chain
@@ -199,6 +211,18 @@ class Mi355Backend:
         # primitives this core exists for, composed as the Groth16 wrap
         # composes them, with no PCIe hop between them.
         n = 1 << self.msm_log2
+        if self.composition == "quotient":
+            try:
+                msm_out, ntt_out = self._prove_quotient(
+                    ea, n, seed, statement, kplans)
+            finally:
+                for kp in kplans or ():
+                    kp.destroy()
+            proof = {"msm": msm_out,
+                     "ntt_digest": hashlib.sha256(ntt_out).digest()}
+            if statement is not None:
+                proof["statement"] = statement
+            return proof
         plan = ea.MsmPlan(n)
         nplan = ea.NttPlan(n)
         try:
@@ -224,6 +248,37 @@ class Mi355Backend:
         if statement is not None:
             proof["statement"] = statement
         return proof
+
+    def _prove_quotient(self, ea, n, seed, statement, kplans):
+        """composition="quotient": a, b -> c = a (.) b -> h on device, h
+        feeds the MSM through the same on-device handoff.  Returns (MSM
+        result, h bytes)."""
+        from . import witness as W
+        plan = ea.MsmPlan(n)
+        qplan = ea.QuotPlan(n)
+        nplan = None
+        try:
+            plan.gen_points(0)
+            if kplans:
+                commitment = bytes.fromhex(statement["commitment"])
+                nplan = ea.NttPlan(n)
+                nplan.fill_from_digests(kplans[-1], commitment)
+                qplan.load_from_ntt(0, nplan)
+                nplan.fill_from_digests(kplans[-1],
+                                        W.quotient_domain_b(commitment))
+                qplan.load_from_ntt(1, nplan)
+            else:
+                qplan.upload(0, ea.gen_fr(seed, n))
+                qplan.upload(1, ea.gen_fr((seed + 1) % (1 << 64), n))
+            qplan.mul_ab_into_c()
+            qplan.run()
+            plan.scalars_from_ntt(qplan, 0)
+            return plan.run(), qplan.download()
+        finally:
+            plan.destroy()
+            qplan.destroy()
+            if nplan is not None:
+                nplan.destroy()
 
     def verify(self, proof) -> None:
         if len(proof.get("msm", b"")) != 64:

@@ -287,6 +287,19 @@ def wrap_vector(hashes, domain: bytes, n: int) -> bytes:
     return bytes(out)
 
 
+QUOTIENT_B_TAG = b"ethrex_amd/quotient/b/v1"
+
+
+def quotient_domain_b(commitment: bytes) -> bytes:
+    """Domain of the quotient composition's second vector: a is wrap vector
+    v1 under the statement commitment, b is wrap vector v1 under
+    keccak256(commitment || QUOTIENT_B_TAG) — same digests, independent
+    expansion (Mi355Backend(composition="quotient"))."""
+    if len(commitment) != 32:
+        raise ValueError("quotient_domain_b: commitment is 32 bytes")
+    return keccak256(commitment + QUOTIENT_B_TAG)
+
+
 def load_witness_fixture(path):
     """Load the committed hoodi witness fixture (tests/golden/*.json.gz,
     extracted from the reference's fixtures/cache/rpc_prover cache)."""

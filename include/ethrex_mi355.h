@@ -178,6 +178,49 @@ int ethrex_mi355_ntt_fill_from_digests(em_ntt_plan *plan,
 /* HIP-event time of the last fill (tree levels + expansion), milliseconds */
 int ethrex_mi355_ntt_last_fill_ms(em_ntt_plan *plan, double *ms);
 
+/* ---- coset transforms and the Groth16 quotient polynomial H (DESIGN.md
+ * "Quotient polynomial").  Coset generator g = 5 (the gnark-crypto /
+ * arkworks generator of BN254 Fr); w as for the plain transform.
+ *   coset forward:  A_j = sum_i a_i g^i w^(ij)
+ *   coset inverse:  a_i = g^-i n^-1 sum_j A_j w^(-ij)
+ * Same buffer rules as ethrex_mi355_ntt_run; the plain transforms of the
+ * plan are unaffected.  EM_NTT_COSET_UNFUSED=1 (read once per process)
+ * forces the standalone scaling pass on every path (A/B measurement). ---- */
+int ethrex_mi355_ntt_run_coset(em_ntt_plan *plan, int inverse);
+int ethrex_mi355_bn254_fr_coset_ntt(uint8_t *elems32, size_t n, int inverse);
+
+/* Quotient of three evaluation vectors a, b, c (values on the n-point
+ * domain, natural order): with x~ = coset_fwd(intt(x)),
+ *   e_j = (a~_j * b~_j - c~_j) * (g^n - 1)^-1,   h = coset_inv(e)
+ * — n coefficients, natural order; for c = a (.) b the exact quotient of
+ * A*B - C by X^n - 1.  The plan owns one twiddle set, three resident
+ * vectors and one work buffer; n a power of two <= 2^28.
+ * EM_ERR_INPUT: null pointer, `which` outside 0..2, bad n, non-canonical
+ * element on upload, mul_ab_into_c without a and b loaded, quot_run
+ * unless all three slots were loaded since the last run, download /
+ * device_data before any run (or after slot a was reloaded). */
+typedef struct em_quot_plan em_quot_plan;
+int ethrex_mi355_quot_plan_create(size_t n, em_quot_plan **plan);
+int ethrex_mi355_quot_plan_destroy(em_quot_plan *plan);
+/* which: 0 = a, 1 = b, 2 = c */
+int ethrex_mi355_quot_upload(em_quot_plan *plan, int which,
+                             const uint8_t *elems32);
+/* copy n resident fe4m elements device-to-device, e.g. from
+ * ethrex_mi355_ntt_device_data (after a fill or a run) */
+int ethrex_mi355_quot_load_device(em_quot_plan *plan, int which,
+                                  const void *d_fe4m);
+/* c = a (.) b, element-wise; marks slot c loaded */
+int ethrex_mi355_quot_mul_ab_into_c(em_quot_plan *plan);
+/* h = quotient(a, b, c); consumes the three slots */
+int ethrex_mi355_quot_run(em_quot_plan *plan);
+int ethrex_mi355_quot_download(em_quot_plan *plan, uint8_t *elems32);
+/* device pointer to h (fe4m), valid until the next load/run/destroy;
+ * feeds ethrex_mi355_msm_scalars_from_ntt unchanged */
+int ethrex_mi355_quot_device_data(em_quot_plan *plan, const void **ptr,
+                                  size_t *n);
+/* [0]=3 iNTT, [1]=3 coset NTT, [2]=pointwise, [3]=coset iNTT, [4]=total (ms) */
+int ethrex_mi355_quot_last_times(em_quot_plan *plan, double times_ms[5]);
+
 /* ---- deterministic input generation (host-side; the product restatement
  *      of BASELINE.md's xoshiro256++/splitmix64 scheme; parity-tested
  *      against the oracle's independent restatement) ---- */
