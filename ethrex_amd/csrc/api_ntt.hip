@@ -30,20 +30,16 @@ struct ntt_tw {
     bool fused2 = false;      // two-level four-step (25 <= logn <= 26)
     int logN1 = 0, logN2 = 0;
     int logM1 = 0, logM2 = 0; // inner split of N2 (fused2)
-    fe9 *d_tw = nullptr;      // fallback: forward twiddles, n/2
-    fe9 *d_tw_inv = nullptr;
-    fe4 *d_twfull = nullptr;      // fused: TW2[c][k] = w^(k*c), streamed
-    fe4 *d_twfull_inv = nullptr;
-    fe9 *d_twrow1 = nullptr;      // fused: N1/2 row twiddles (+inv)
-    fe9 *d_twrow1_inv = nullptr;
-    fe9 *d_twrow2 = nullptr;      // fused: N2/2 (+inv)
-    fe9 *d_twrow2_inv = nullptr;
-    fe4 *d_twfull2 = nullptr;     // fused2: inner TW2B[c][k], size N2 (+inv)
-    fe4 *d_twfull2_inv = nullptr;
-    fe9 *d_twrowA = nullptr;      // fused2: inner M1/2 row twiddles (+inv)
-    fe9 *d_twrowA_inv = nullptr;
-    fe9 *d_twrowB = nullptr;      // fused2: inner M2/2 (+inv)
-    fe9 *d_twrowB_inv = nullptr;
+    // the direction-dependent tables: dir[0] forward, dir[1] inverse
+    struct dir_tw {
+        fe9 *tw = nullptr;    // fallback: stage twiddles, n/2
+        fe4 *full = nullptr;  // fused: TW2[c][k] = w^(k*c), streamed
+        fe9 *row1 = nullptr;  // fused: N1/2 row twiddles
+        fe9 *row2 = nullptr;  // fused: N2/2
+        fe4 *full2 = nullptr; // fused2: inner TW2B[c][k], size N2
+        fe9 *rowA = nullptr;  // fused2: inner M1/2 row twiddles
+        fe9 *rowB = nullptr;  // fused2: inner M2/2
+    } dir[2];
     fe9 *d_ninv = nullptr;        // 1/n (fe9 Montgomery)
     // coset tables (built on first coset use, ntt_tw_coset_init).  Index
     // split i = hi * 2^lo_bits + lo with cs_logA high bits / cs_logB low
@@ -74,81 +70,71 @@ struct em_ntt_plan : ntt_tw {
     double last_fill_ms = 0;
 };
 
-// build w2k powers on host and launch k_gen_twiddles: tw[j] = w^j, j < count
-static int gen_tw_table(fe9 *d_out, size_t count, int bits, bool inverse,
-                        int log_size /* transform size 2^log_size */) {
-    fe9 w = fe9_load(inverse ? bn254::FR9_W28_INV : bn254::FR9_W28);
-    for (int k = bn254::FR_TWO_ADICITY; k > log_size; k--)
-        w = mont_sqr9<Fr9T>(w);
-    fe9 w2k[32];
-    w2k[0] = log_size == 0 ? fe9_load(bn254::FR9_ONE) : w;
-    for (int k = 1; k < bits && k < 32; k++) w2k[k] = mont_sqr9<Fr9T>(w2k[k - 1]);
-    fe9 *d_w2k;
-    HIP_TRY(hipMalloc(&d_w2k, sizeof(w2k)));
-    HIP_TRY(hipMemcpy(d_w2k, w2k, sizeof(w2k), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_gen_twiddles, dim3(blocks_for(count, 256)), dim3(256),
-                       0, 0, d_out, count, d_w2k, bits);
-    HIP_TRY(hipDeviceSynchronize());
-    hipError_t e2 = hipFree(d_w2k);
-    (void)e2;
+// ---- table generation ----
+
+static fe9 sqr_times(fe9 x, int k) {
+    for (int i = 0; i < k; i++) x = mont_sqr9<Fr9T>(x);
+    return x;
+}
+
+// the 2^log_size-th root of unity of that direction (Montgomery)
+static fe9 root_of_unity(int log_size, bool inverse) {
+    return sqr_times(fe9_load(inverse ? bn254::FR9_W28_INV : bn254::FR9_W28),
+                     bn254::FR_TWO_ADICITY - log_size);
+}
+
+// the generators' square ladder: b2k[k] = base^(2^k), k < LADDER_BITS
+constexpr int LADDER_BITS = 32;
+static void ladder_fill(fe9 b2k[LADDER_BITS], fe9 base) {
+    b2k[0] = base;
+    for (int k = 1; k < LADDER_BITS; k++) b2k[k] = mont_sqr9<Fr9T>(b2k[k - 1]);
+}
+
+// one device scratch buffer for the ladder per ntt_tw_create /
+// ntt_tw_coset_init call, freed on every exit path.  set() and the generator
+// launches are all on the null stream, so a ladder is not overwritten
+// before the launch reading it has run.
+struct gen_ladder {
+    fe9 *d = nullptr;
+    ~gen_ladder() { (void)hipFree(d); }
+    int set(fe9 base) {
+        fe9 b2k[LADDER_BITS];
+        ladder_fill(b2k, base);
+        if (!d) HIP_TRY(hipMalloc((void **)&d, sizeof(b2k)));
+        HIP_TRY(hipMemcpy(d, b2k, sizeof(b2k), hipMemcpyHostToDevice));
+        return EM_OK;
+    }
+};
+
+// *out (allocated here unless it already is) [j] = s * base^j, j < count
+static int gen_pow_table(gen_ladder &L, fe9 **out, size_t count, fe9 base,
+                         fe9 s) {
+    if (!*out) HIP_TRY(hipMalloc((void **)out, count * sizeof(fe9)));
+    int rc = L.set(base);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_gen_pow, dim3(blocks_for(count, 256)), dim3(256), 0,
+                       0, *out, count, L.d, LADDER_BITS, s);
     return EM_OK;
 }
 
-// row-kernel dispatch for the one-level path: default radix-2^3 at 512
-// threads; EM_NTT_R4=1 selects the radix-2^2 variant, EM_NTT_TD sets its
-// block size (512/768/1024) — A/B occupancy experiment.
-static void launch_row(uint32_t nrows, int logM, fe4 *data,
-                       const fe9 *tw_row, const fe4 *tw2, const fe9 *scale) {
-    size_t lds = (((size_t)1 << logM) + (((size_t)1 << logM) >> 6)) *
-                 sizeof(fe9);
-    // default: radix-2^2 at 1024 threads (A/B best: 3.28 ms vs 3.38 for
-    // the radix-2^3/512 shape at 2^24 — 4 waves/SIMD hides the LDS+mul
-    // latency better than fewer round trips at 2 waves).  EM_NTT_R8
-    // selects the radix-2^3 variant.
-    static int r4 = std::getenv("EM_NTT_R8") ? 0 : 1;
-    static int td = std::getenv("EM_NTT_TD") ? atoi(std::getenv("EM_NTT_TD"))
-                                             : 1024;
-    if (r4) {
-        hipLaunchKernelGGL(k_ntt_row4, dim3(nrows), dim3(td), lds, 0, data,
-                           logM, tw_row, tw2, scale, 0xffffffffu);
-    } else {
-        hipLaunchKernelGGL(k_ntt_row, dim3(nrows), dim3(512), lds, 0, data,
-                           logM, tw_row, tw2, scale, 0xffffffffu);
-    }
+// row twiddles of a 2^log_size transform: (*out)[j] = w^j, j < 2^(log_size-1)
+static int gen_row_table(gen_ladder &L, fe9 **out, int log_size, bool inverse) {
+    return gen_pow_table(L, out, (size_t)1 << (log_size > 0 ? log_size - 1 : 0),
+                         root_of_unity(log_size, inverse),
+                         fe9_load(bn254::FR9_ONE));
 }
 
-// the same dispatch for the coset instantiations (COSET = 1: P1 of the
-// forward transform, 2: P2 of the inverse; see ntt_kernels.h)
-template <int COSET>
-static void launch_row_coset(uint32_t nrows, int logM, fe4 *data,
-                             const fe9 *tw_row, const fe4 *tw2,
-                             const fe9 *cs_elem, const fe9 *cs_row) {
-    size_t lds = (((size_t)1 << logM) + (((size_t)1 << logM) >> 6)) *
-                 sizeof(fe9);
-    static int r4 = std::getenv("EM_NTT_R8") ? 0 : 1;
-    static int td = std::getenv("EM_NTT_TD") ? atoi(std::getenv("EM_NTT_TD"))
-                                             : 1024;
-    if (r4) {
-        hipLaunchKernelGGL(k_ntt_row4_coset<COSET>, dim3(nrows), dim3(td),
-                           lds, 0, data, logM, tw_row, tw2, cs_elem, cs_row);
-    } else {
-        hipLaunchKernelGGL(k_ntt_row_coset<COSET>, dim3(nrows), dim3(512),
-                           lds, 0, data, logM, tw_row, tw2, cs_elem, cs_row);
-    }
-}
-
-// out[j] = s * base^j, j < count (the coset tables)
-static int gen_pow_table(fe9 *d_out, size_t count, fe9 base, fe9 s) {
-    fe9 b2k[32];
-    b2k[0] = base;
-    for (int k = 1; k < 32; k++) b2k[k] = mont_sqr9<Fr9T>(b2k[k - 1]);
-    fe9 *d_b2k;
-    HIP_TRY(hipMalloc(&d_b2k, sizeof(b2k)));
-    HIP_TRY(hipMemcpy(d_b2k, b2k, sizeof(b2k), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_gen_pow, dim3(blocks_for(count, 256)), dim3(256), 0,
-                       0, d_out, count, d_b2k, 32, s);
-    HIP_TRY(hipDeviceSynchronize());
-    (void)hipFree(d_b2k);
+// reordered streamed table TW2[c*M + k] = w^(k*c) (fe4m), c < rows, of a
+// 2^log_size = M*rows transform: P1's per-row twiddle read becomes a
+// coalesced stream instead of a stride-c gather over an n-sized table (a
+// full cache line per element).
+static int gen_tw2_table(gen_ladder &L, fe4 **out, uint32_t M, size_t rows,
+                         int log_size, bool inverse) {
+    if (!*out) HIP_TRY(hipMalloc((void **)out, (size_t)M * rows * sizeof(fe4)));
+    int rc = L.set(root_of_unity(log_size, inverse));
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_gen_tw2, dim3(blocks_for((size_t)M * rows, 256)),
+                       dim3(256), 0, 0, *out, M, rows, L.d, log_size);
     return EM_OK;
 }
 
@@ -160,34 +146,70 @@ static fe9 coset_gen() {
     return to_mont9<Fr9T>(five);
 }
 
-static fe9 sqr_times(fe9 x, int k) {
-    for (int i = 0; i < k; i++) x = mont_sqr9<Fr9T>(x);
-    return x;
+// ---- row-kernel dispatch ----
+// Default: radix-2^2 at 1024 threads (A/B best: 3.28 ms vs 3.38 for the
+// radix-2^3/512 shape at 2^24 — 4 waves/SIMD hides the LDS+mul latency
+// better than fewer round trips at 2 waves).  EM_NTT_R8 selects the
+// radix-2^3 kernels at 512 threads; EM_NTT_TD sets the radix-2^2 block
+// size (an A/B knob, not validated).  Both are read once per process.
+struct row_cfg {
+    bool r8;
+    int td;
+};
+static const row_cfg &row_config() {
+    static const row_cfg c = {
+        std::getenv("EM_NTT_R8") != nullptr,
+        std::getenv("EM_NTT_TD") ? atoi(std::getenv("EM_NTT_TD")) : 1024};
+    return c;
 }
 
-// reordered streamed table TW2[c*M + k] = w^(k*c) (fe4m), c < rows:
-// P1's per-row twiddle read becomes a coalesced stream instead of a
-// stride-c gather over an n-sized table (a full cache line per element).
-static int gen_tw2_table(fe4 *d_out, uint32_t M, size_t rows, bool inverse,
-                         int log_size /* transform size 2^log_size */) {
-    fe9 w = fe9_load(inverse ? bn254::FR9_W28_INV : bn254::FR9_W28);
-    for (int k = bn254::FR_TWO_ADICITY; k > log_size; k--)
-        w = mont_sqr9<Fr9T>(w);
-    fe9 w2k[32];
-    w2k[0] = log_size == 0 ? fe9_load(bn254::FR9_ONE) : w;
-    for (int k = 1; k < log_size && k < 32; k++)
-        w2k[k] = mont_sqr9<Fr9T>(w2k[k - 1]);
-    fe9 *d_w2k;
-    HIP_TRY(hipMalloc(&d_w2k, sizeof(w2k)));
-    HIP_TRY(hipMemcpy(d_w2k, w2k, sizeof(w2k), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_gen_tw2, dim3(blocks_for((size_t)M * rows, 256)),
-                       dim3(256), 0, 0, d_out, M, rows, d_w2k, log_size);
-    HIP_TRY(hipDeviceSynchronize());
-    (void)hipFree(d_w2k);
+// skewed LDS row of 2^logM elements: M + M/64 fe9 slots
+static size_t row_lds_bytes(int logM) {
+    size_t M = (size_t)1 << logM;
+    return (M + (M >> 6)) * sizeof(fe9);
+}
+
+// the 4096-element rows need 146 KiB of dynamic LDS (opt-in above 64K);
+// applied once (per device, and a process uses one)
+static int row_lds_opt_in() {
+    static const void *const kernels[] = {
+        (const void *)&k_ntt_row,          (const void *)&k_ntt_row4,
+        (const void *)&k_ntt_row_coset<1>, (const void *)&k_ntt_row_coset<2>,
+        (const void *)&k_ntt_row4_coset<1>, (const void *)&k_ntt_row4_coset<2>};
+    static int done_dev = -1;
+    int dev;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev == done_dev) return EM_OK;
+    for (const void *k : kernels)
+        HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)row_lds_bytes(12)));
+    done_dev = dev;
     return EM_OK;
 }
 
-static void ntt_tw_free(ntt_tw *p);
+// one row pass: nrows blocks, one 2^logM row each.  COSET = 0: plain
+// (scale may be null); 1: P1 of the coset forward transform, 2: P2 of the
+// coset inverse (cs_elem / cs_row, see ntt_kernels.h).
+template <int COSET>
+static void launch_row(uint32_t nrows, int logM, fe4 *data, const fe9 *tw_row,
+                       const fe4 *tw2, const fe9 *scale,
+                       const fe9 *cs_elem = nullptr,
+                       const fe9 *cs_row = nullptr) {
+    const row_cfg &c = row_config();
+    const dim3 grid(nrows), block(c.r8 ? 512 : c.td);
+    const size_t lds = row_lds_bytes(logM);
+    if constexpr (COSET == 0) {
+        hipLaunchKernelGGL(c.r8 ? k_ntt_row : k_ntt_row4, grid, block, lds, 0,
+                           data, logM, tw_row, tw2, scale, 0xffffffffu);
+    } else {
+        hipLaunchKernelGGL(c.r8 ? k_ntt_row_coset<COSET>
+                                : k_ntt_row4_coset<COSET>,
+                           grid, block, lds, 0, data, logM, tw_row, tw2,
+                           cs_elem, cs_row);
+    }
+}
+
+// ---- twiddle set ----
 
 // n a power of two <= 2^28 (checked by the callers); on failure the
 // caller frees what was allocated (ntt_tw_free)
@@ -206,114 +228,55 @@ static int ntt_tw_create(ntt_tw *p, size_t n) {
         p->fused = false;
         p->fused2 = true;
     }
-    size_t half = n > 1 ? n / 2 : 1;
-    hipError_t e = hipSuccess;
-    auto mal = [&](void **ptr, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(ptr, bytes);
-    };
-    if (p->fused || p->fused2) {
-        if (p->fused) {
-            p->logN1 = (logn + 1) / 2;
-            p->logN2 = logn / 2;
-        } else {
-            // two-level: outer P1 rows of 2^logN1 (through the batched
-            // small-row kernel when logN1 <= 10, the dynamic-LDS row
-            // kernel for 11-12); inner four-step over the 2^logN2 rows.
-            // EM_NTT_SPLIT overrides logN1 for A/B measurement.
-            p->logN1 = logn >= 25 ? 12 : logn - 16;
-            if (const char *e = std::getenv("EM_NTT_SPLIT")) {
-                int v = atoi(e);
-                if (v >= logn - 16 && v <= 12 && logn - v >= 10)
-                    p->logN1 = v;
-            }
-            p->logN2 = logn - p->logN1;
-            p->logM1 = (p->logN2 + 1) / 2;
-            p->logM2 = p->logN2 / 2;
+    if (p->fused) {
+        p->logN1 = (logn + 1) / 2;
+        p->logN2 = logn / 2;
+    } else if (p->fused2) {
+        // two-level: outer P1 rows of 2^logN1 (through the batched
+        // small-row kernel when logN1 <= 10, the dynamic-LDS row
+        // kernel for 11-12); inner four-step over the 2^logN2 rows.
+        // EM_NTT_SPLIT overrides logN1 for A/B measurement.
+        p->logN1 = logn >= 25 ? 12 : logn - 16;
+        if (const char *e = std::getenv("EM_NTT_SPLIT")) {
+            int v = atoi(e);
+            if (v >= logn - 16 && v <= 12 && logn - v >= 10)
+                p->logN1 = v;
         }
-        mal((void **)&p->d_twfull, n * sizeof(fe4));
-        mal((void **)&p->d_twfull_inv, n * sizeof(fe4));
-        mal((void **)&p->d_twrow1, ((size_t)1 << (p->logN1 - 1)) * sizeof(fe9));
-        mal((void **)&p->d_twrow1_inv, ((size_t)1 << (p->logN1 - 1)) * sizeof(fe9));
-        mal((void **)&p->d_twrow2,
-            ((size_t)1 << (p->logN2 > 0 ? p->logN2 - 1 : 0)) * sizeof(fe9));
-        mal((void **)&p->d_twrow2_inv,
-            ((size_t)1 << (p->logN2 > 0 ? p->logN2 - 1 : 0)) * sizeof(fe9));
-        mal((void **)&p->d_ninv, sizeof(fe9));
-        if (p->fused2) {
-            mal((void **)&p->d_twfull2, ((size_t)1 << p->logN2) * sizeof(fe4));
-            mal((void **)&p->d_twfull2_inv,
-                ((size_t)1 << p->logN2) * sizeof(fe4));
-            mal((void **)&p->d_twrowA,
-                ((size_t)1 << (p->logM1 - 1)) * sizeof(fe9));
-            mal((void **)&p->d_twrowA_inv,
-                ((size_t)1 << (p->logM1 - 1)) * sizeof(fe9));
-            mal((void **)&p->d_twrowB,
-                ((size_t)1 << (p->logM2 - 1)) * sizeof(fe9));
-            mal((void **)&p->d_twrowB_inv,
-                ((size_t)1 << (p->logM2 - 1)) * sizeof(fe9));
-        }
-    } else {
-        mal((void **)&p->d_tw, half * sizeof(fe9));
-        mal((void **)&p->d_tw_inv, half * sizeof(fe9));
+        p->logN2 = logn - p->logN1;
+        p->logM1 = (p->logN2 + 1) / 2;
+        p->logM2 = p->logN2 / 2;
     }
-    // the 4096-element rows need 146 KiB of dynamic LDS (opt-in above 64K)
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(
-            (const void *)&k_ntt_row,
-            hipFuncAttributeMaxDynamicSharedMemorySize,
-            (int)((4096 + 64) * sizeof(fe9)));
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute(
-            (const void *)&k_ntt_row4,
-            hipFuncAttributeMaxDynamicSharedMemorySize,
-            (int)((4096 + 64) * sizeof(fe9)));
-    if (e != hipSuccess) return hip_fail(e, "ntt_plan_create");
-    if (p->fused || p->fused2) {
-        int rc2;
-        uint32_t N1g = 1u << p->logN1;
-        if ((rc2 = gen_tw2_table(p->d_twfull, N1g, n / N1g, false, logn)))
-            return rc2;
-        if ((rc2 = gen_tw2_table(p->d_twfull_inv, N1g, n / N1g, true, logn)))
-            return rc2;
-        if ((rc2 = gen_tw_table(p->d_twrow1, (size_t)1 << (p->logN1 - 1),
-                                p->logN1, false, p->logN1))) return rc2;
-        if ((rc2 = gen_tw_table(p->d_twrow1_inv, (size_t)1 << (p->logN1 - 1),
-                                p->logN1, true, p->logN1))) return rc2;
-        if ((rc2 = gen_tw_table(p->d_twrow2, (size_t)1 << (p->logN2 - 1),
-                                p->logN2, false, p->logN2))) return rc2;
-        if ((rc2 = gen_tw_table(p->d_twrow2_inv, (size_t)1 << (p->logN2 - 1),
-                                p->logN2, true, p->logN2))) return rc2;
-        if (p->fused2) {
-            size_t n2 = (size_t)1 << p->logN2;
-            uint32_t M1g = 1u << p->logM1;
-            if ((rc2 = gen_tw2_table(p->d_twfull2, M1g, n2 / M1g, false,
-                                     p->logN2))) return rc2;
-            if ((rc2 = gen_tw2_table(p->d_twfull2_inv, M1g, n2 / M1g, true,
-                                     p->logN2))) return rc2;
-            if ((rc2 = gen_tw_table(p->d_twrowA, (size_t)1 << (p->logM1 - 1),
-                                    p->logM1, false, p->logM1))) return rc2;
-            if ((rc2 = gen_tw_table(p->d_twrowA_inv,
-                                    (size_t)1 << (p->logM1 - 1), p->logM1,
-                                    true, p->logM1))) return rc2;
-            if ((rc2 = gen_tw_table(p->d_twrowB, (size_t)1 << (p->logM2 - 1),
-                                    p->logM2, false, p->logM2))) return rc2;
-            if ((rc2 = gen_tw_table(p->d_twrowB_inv,
-                                    (size_t)1 << (p->logM2 - 1), p->logM2,
-                                    true, p->logM2))) return rc2;
+    int rc = row_lds_opt_in();
+    if (rc) return rc;
+    gen_ladder L;
+    for (int inv = 0; inv < 2; inv++) {
+        ntt_tw::dir_tw &d = p->dir[inv];
+        if (!p->fused && !p->fused2) {
+            if ((rc = gen_row_table(L, &d.tw, logn, inv))) return rc;
+            continue;
         }
+        uint32_t N1 = 1u << p->logN1;
+        if ((rc = gen_tw2_table(L, &d.full, N1, n / N1, logn, inv))) return rc;
+        if ((rc = gen_row_table(L, &d.row1, p->logN1, inv))) return rc;
+        if ((rc = gen_row_table(L, &d.row2, p->logN2, inv))) return rc;
+        if (!p->fused2) continue;
+        uint32_t M1 = 1u << p->logM1;
+        if ((rc = gen_tw2_table(L, &d.full2, M1, ((size_t)1 << p->logN2) / M1,
+                                p->logN2, inv))) return rc;
+        if ((rc = gen_row_table(L, &d.rowA, p->logM1, inv))) return rc;
+        if ((rc = gen_row_table(L, &d.rowB, p->logM2, inv))) return rc;
+    }
+    if (p->fused || p->fused2) {
         fe9 ninv = fe9_load(bn254::FR9_INV_POW2[logn]);
+        HIP_TRY(hipMalloc((void **)&p->d_ninv, sizeof(fe9)));
         HIP_TRY(hipMemcpy(p->d_ninv, &ninv, sizeof(fe9), hipMemcpyHostToDevice));
-    } else {
-        int rc2;
-        if ((rc2 = gen_tw_table(p->d_tw, half, logn ? logn : 1, false, logn)))
-            return rc2;
-        if ((rc2 = gen_tw_table(p->d_tw_inv, half, logn ? logn : 1, true, logn)))
-            return rc2;
     }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     return EM_OK;
 }
 
-// coset tables + the coset kernels' LDS opt-in, on first coset use
+// coset tables, on first coset use
 static int ntt_tw_coset_init(ntt_tw *p) {
     if (p->coset_ok) return EM_OK;
     if (p->fused) {
@@ -324,37 +287,20 @@ static int ntt_tw_coset_init(ntt_tw *p) {
         p->cs_logB = p->logn / 2;
     }
     size_t nA = (size_t)1 << p->cs_logA, nB = (size_t)1 << p->cs_logB;
-    if (!p->cs_f_hi) HIP_TRY(hipMalloc((void **)&p->cs_f_hi, nA * sizeof(fe9)));
-    if (!p->cs_f_lo) HIP_TRY(hipMalloc((void **)&p->cs_f_lo, nB * sizeof(fe9)));
-    if (!p->cs_i_hi) HIP_TRY(hipMalloc((void **)&p->cs_i_hi, nB * sizeof(fe9)));
-    if (!p->cs_i_lo) HIP_TRY(hipMalloc((void **)&p->cs_i_lo, nA * sizeof(fe9)));
-    HIP_TRY(hipFuncSetAttribute(
-        (const void *)&k_ntt_row_coset<1>,
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)((4096 + 64) * sizeof(fe9))));
-    HIP_TRY(hipFuncSetAttribute(
-        (const void *)&k_ntt_row_coset<2>,
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)((4096 + 64) * sizeof(fe9))));
-    HIP_TRY(hipFuncSetAttribute(
-        (const void *)&k_ntt_row4_coset<1>,
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)((4096 + 64) * sizeof(fe9))));
-    HIP_TRY(hipFuncSetAttribute(
-        (const void *)&k_ntt_row4_coset<2>,
-        hipFuncAttributeMaxDynamicSharedMemorySize,
-        (int)((4096 + 64) * sizeof(fe9))));
     fe9 one = fe9_load(bn254::FR9_ONE);
     fe9 g = coset_gen();
     fe9 ginv = mont_inv9<Fr9T>(g);
     fe9 ninv = fe9_load(bn254::FR9_INV_POW2[p->logn]);
+    gen_ladder L;
     int rc;
-    if ((rc = gen_pow_table(p->cs_f_hi, nA, sqr_times(g, p->cs_logB), one)))
+    if ((rc = gen_pow_table(L, &p->cs_f_hi, nA, sqr_times(g, p->cs_logB), one)))
         return rc;
-    if ((rc = gen_pow_table(p->cs_f_lo, nB, g, one))) return rc;
-    if ((rc = gen_pow_table(p->cs_i_hi, nB, sqr_times(ginv, p->cs_logA), one)))
-        return rc;
-    if ((rc = gen_pow_table(p->cs_i_lo, nA, ginv, ninv))) return rc;
+    if ((rc = gen_pow_table(L, &p->cs_f_lo, nB, g, one))) return rc;
+    if ((rc = gen_pow_table(L, &p->cs_i_hi, nB, sqr_times(ginv, p->cs_logA),
+                            one))) return rc;
+    if ((rc = gen_pow_table(L, &p->cs_i_lo, nA, ginv, ninv))) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     p->coset_ok = true;
     return EM_OK;
 }
@@ -392,25 +338,13 @@ extern "C" int ethrex_mi355_ntt_plan_create(size_t n, em_ntt_plan **plan) {
 }
 
 static void ntt_tw_free(ntt_tw *p) {
-    (void)hipFree(p->cs_f_hi);
-    (void)hipFree(p->cs_f_lo);
-    (void)hipFree(p->cs_i_hi);
-    (void)hipFree(p->cs_i_lo);
-    (void)hipFree(p->d_tw);
-    (void)hipFree(p->d_tw_inv);
-    (void)hipFree(p->d_twfull);
-    (void)hipFree(p->d_twfull2);
-    (void)hipFree(p->d_twfull2_inv);
-    (void)hipFree(p->d_twrowA);
-    (void)hipFree(p->d_twrowA_inv);
-    (void)hipFree(p->d_twrowB);
-    (void)hipFree(p->d_twrowB_inv);
-    (void)hipFree(p->d_twfull_inv);
-    (void)hipFree(p->d_twrow1);
-    (void)hipFree(p->d_twrow1_inv);
-    (void)hipFree(p->d_twrow2);
-    (void)hipFree(p->d_twrow2_inv);
-    (void)hipFree(p->d_ninv);
+    for (fe9 *t : {p->cs_f_hi, p->cs_f_lo, p->cs_i_hi, p->cs_i_lo, p->d_ninv})
+        (void)hipFree(t);
+    for (ntt_tw::dir_tw &d : p->dir)
+        for (void *t : {(void *)d.tw, (void *)d.full, (void *)d.row1,
+                        (void *)d.row2, (void *)d.full2, (void *)d.rowA,
+                        (void *)d.rowB})
+            (void)hipFree(t);
 }
 
 extern "C" int ethrex_mi355_ntt_plan_destroy(em_ntt_plan *p) {
@@ -429,16 +363,32 @@ extern "C" int ethrex_mi355_ntt_plan_destroy(em_ntt_plan *p) {
     return EM_OK;
 }
 
+// n canonical big-endian elements -> fe4m in d_out, through the n*32-byte
+// device staging area d_stage; EM_ERR_INPUT if an element is >= r
+static int fr_upload_be(const uint8_t *elems32, size_t n, uint8_t *d_stage,
+                        fe4 *d_out, uint32_t *d_err) {
+    HIP_TRY(hipMemset(d_err, 0, 4));
+    HIP_TRY(hipMemcpy(d_stage, elems32, n * 32, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_fr_from_be, dim3(blocks_for(n, 256)), dim3(256), 0, 0,
+                       d_stage, d_out, n, d_err);
+    uint32_t err;
+    HIP_TRY(hipMemcpy(&err, d_err, 4, hipMemcpyDeviceToHost));
+    return err ? EM_ERR_INPUT : EM_OK;
+}
+
+// the reverse: n fe4m elements of d_in -> big-endian bytes on the host
+static int fr_download_be(uint8_t *elems32, size_t n, const fe4 *d_in,
+                          uint8_t *d_stage) {
+    hipLaunchKernelGGL(k_fr_to_be, dim3(blocks_for(n, 256)), dim3(256), 0, 0,
+                       d_in, d_stage, n);
+    HIP_TRY(hipMemcpy(elems32, d_stage, n * 32, hipMemcpyDeviceToHost));
+    return EM_OK;
+}
+
 extern "C" int ethrex_mi355_ntt_upload(em_ntt_plan *p, const uint8_t *elems32) {
     if (!p || !elems32) return EM_ERR_INPUT;
-    HIP_TRY(hipMemset(p->d_err, 0, 4));
-    HIP_TRY(hipMemcpy(p->d_bytes, elems32, p->n * 32, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_fr_from_be, dim3(blocks_for(p->n, 256)), dim3(256), 0, 0,
-                       p->d_bytes, p->d_data, p->n, p->d_err);
     p->cur = 0;
-    uint32_t err;
-    HIP_TRY(hipMemcpy(&err, p->d_err, 4, hipMemcpyDeviceToHost));
-    return err ? EM_ERR_INPUT : EM_OK;
+    return fr_upload_be(elems32, p->n, p->d_bytes, p->d_data, p->d_err);
 }
 
 // wrap vector v1: expand m device-resident keccak digests into
@@ -516,39 +466,52 @@ static int ntt_exec(const ntt_tw *p, fe4 *cur, fe4 *oth, int inverse,
     const bool cs_fused = coset && p->fused && !unfused;
     const bool cs_pass = coset && !cs_fused;   // standalone scale pass
     const fe9 *ninv = (inverse && !coset) ? p->d_ninv : (const fe9 *)nullptr;
+    const ntt_tw::dir_tw &d = p->dir[inverse ? 1 : 0];
+    // four-step shape: n = N1 * N2, and N2 = M1 * M2 on the two-level path
+    const uint32_t N1 = 1u << p->logN1, N2 = 1u << p->logN2;
+    const uint32_t M1 = 1u << p->logM1, M2 = 1u << p->logM2;
+    // `batch` R x C matrices src -> their transposes dst
+    auto transpose = [](const fe4 *src, fe4 *dst, uint32_t R, uint32_t C,
+                        uint32_t batch) {
+        hipLaunchKernelGGL(k_transpose_fe4, dim3(C / 32, R / 32, batch),
+                           dim3(256), 0, 0, src, dst, R, C);
+    };
+    // `total` elements as packed 2^logM rows, 1024 elements per block
+    auto row_small = [](size_t total, int logM, fe4 *data, const fe9 *tw_row,
+                        const fe4 *tw2, const fe9 *scale, uint32_t cmask) {
+        hipLaunchKernelGGL(k_ntt_row_small, dim3((uint32_t)(total / 1024)),
+                           dim3(512), 0, 0, data, logM, tw_row, tw2, scale,
+                           cmask);
+    };
     *flipped = false;
     if (cs_pass && !inverse)
         hipLaunchKernelGGL(k_coset_scale, dim3(blocks_for(n, 256)), dim3(256),
                            0, 0, cur, n, p->cs_f_hi, p->cs_f_lo, p->cs_logB);
-    if (p->fused) {
-        uint32_t N1 = 1u << p->logN1, N2 = 1u << p->logN2;
+    if (p->fused || p->fused2) {
         // T0: A[r][c] -> A1[c][r]
-        hipLaunchKernelGGL(k_transpose_fe4, dim3(N2 / 32, N1 / 32), dim3(256), 0,
-                           0, cur, oth, N1, N2);
+        transpose(cur, oth, N1, N2, 1);
         if (ev_mid) HIP_TRY(hipEventRecord(*ev_mid, 0));
         // P1: row NTT_N1 over each of the N2 rows + w^(k1*c) twiddle
         if (cs_fused && !inverse)
-            launch_row_coset<1>(N2, p->logN1, oth, p->d_twrow1, p->d_twfull,
-                                p->cs_f_hi, p->cs_f_lo);
+            launch_row<1>(N2, p->logN1, oth, d.row1, d.full, nullptr,
+                          p->cs_f_hi, p->cs_f_lo);
+        else if (p->fused2 && p->logN1 <= 10)
+            row_small(n, p->logN1, oth, d.row1, d.full, nullptr,
+                      0xffffffffu);
         else
-            launch_row(N2, p->logN1,
-                       oth, inverse ? p->d_twrow1_inv : p->d_twrow1,
-                       inverse ? p->d_twfull_inv : p->d_twfull,
-                       (const fe9 *)nullptr);
+            launch_row<0>(N2, p->logN1, oth, d.row1, d.full, nullptr);
         // T1
-        hipLaunchKernelGGL(k_transpose_fe4, dim3(N1 / 32, N2 / 32), dim3(256), 0,
-                           0, oth, cur, N2, N1);
+        transpose(oth, cur, N2, N1, 1);
+    }
+    if (p->fused) {
         // P2: row NTT_N2 (+ 1/n scale on iNTT)
         if (cs_fused && inverse)
-            launch_row_coset<2>(N1, p->logN2, cur, p->d_twrow2_inv,
-                                (const fe4 *)nullptr, p->cs_i_hi, p->cs_i_lo);
+            launch_row<2>(N1, p->logN2, cur, d.row2, nullptr, nullptr,
+                          p->cs_i_hi, p->cs_i_lo);
         else
-            launch_row(N1, p->logN2,
-                       cur, inverse ? p->d_twrow2_inv : p->d_twrow2,
-                       (const fe4 *)nullptr, ninv);
+            launch_row<0>(N1, p->logN2, cur, d.row2, nullptr, ninv);
         // T2: natural order
-        hipLaunchKernelGGL(k_transpose_fe4, dim3(N2 / 32, N1 / 32), dim3(256), 0,
-                           0, cur, oth, N1, N2);
+        transpose(cur, oth, N1, N2, 1);
         *flipped = true;
     } else if (p->fused2) {
         // two-level four-step (25 <= logn <= 26): the outer P2 row length
@@ -557,43 +520,13 @@ static int ntt_exec(const ntt_tw *p, fe4 *cur, fe4 *oth, int inverse,
         // four-step (M1 x M2, both <= 2^7).  The inner transform is
         // natural-in / natural-out, so it composes exactly where the
         // one-level P2 sat.  8 full-array passes instead of logn.
-        uint32_t N1 = 1u << p->logN1, N2 = 1u << p->logN2;
-        uint32_t M1 = 1u << p->logM1, M2 = 1u << p->logM2;
-        const fe9 *tr1 = inverse ? p->d_twrow1_inv : p->d_twrow1;
-        const fe4 *tf = inverse ? p->d_twfull_inv : p->d_twfull;
-        const fe4 *tf2 = inverse ? p->d_twfull2_inv : p->d_twfull2;
-        const fe9 *trA = inverse ? p->d_twrowA_inv : p->d_twrowA;
-        const fe9 *trB = inverse ? p->d_twrowB_inv : p->d_twrowB;
-        // T0 + P1 + T1: outer column NTTs (length N1) + w_n^(k1 c)
-        hipLaunchKernelGGL(k_transpose_fe4, dim3(N2 / 32, N1 / 32), dim3(256),
-                           0, 0, cur, oth, N1, N2);
-        if (ev_mid) HIP_TRY(hipEventRecord(*ev_mid, 0));
-        if (p->logN1 <= 10) {
-            hipLaunchKernelGGL(k_ntt_row_small, dim3(N2 * N1 / 1024),
-                               dim3(512), 0, 0, oth, p->logN1, tr1, tf,
-                               (const fe9 *)nullptr, 0xffffffffu);
-        } else {
-            launch_row(N2, p->logN1, oth, tr1, tf, (const fe9 *)nullptr);
-        }
-        hipLaunchKernelGGL(k_transpose_fe4, dim3(N1 / 32, N2 / 32), dim3(256),
-                           0, 0, oth, cur, N2, N1);
-        // inner batched four-step over the N1 rows of length N2 = M1*M2
-        hipLaunchKernelGGL(k_transpose_fe4, dim3(M2 / 32, M1 / 32, N1),
-                           dim3(256), 0, 0, cur, oth, M1, M2);
-        hipLaunchKernelGGL(k_ntt_row_small, dim3(N1 * M2 * M1 / 1024),
-                           dim3(512), 0, 0, oth, p->logM1, trA, tf2,
-                           (const fe9 *)nullptr, M2 - 1);  // (see P1 above)
-        hipLaunchKernelGGL(k_transpose_fe4, dim3(M1 / 32, M2 / 32, N1),
-                           dim3(256), 0, 0, oth, cur, M2, M1);
-        hipLaunchKernelGGL(k_ntt_row_small, dim3(N1 * M1 * M2 / 1024),
-                           dim3(512), 0, 0, cur, p->logM2, trB,
-                           (const fe4 *)nullptr,
-                           ninv, 0xffffffffu);
-        hipLaunchKernelGGL(k_transpose_fe4, dim3(M2 / 32, M1 / 32, N1),
-                           dim3(256), 0, 0, cur, oth, M1, M2);
+        transpose(cur, oth, M1, M2, N1);
+        row_small(n, p->logM1, oth, d.rowA, d.full2, nullptr, M2 - 1);
+        transpose(oth, cur, M2, M1, N1);
+        row_small(n, p->logM2, cur, d.rowB, nullptr, ninv, 0xffffffffu);
+        transpose(cur, oth, M1, M2, N1);
         // outer T2 -> natural order
-        hipLaunchKernelGGL(k_transpose_fe4, dim3(N2 / 32, N1 / 32), dim3(256),
-                           0, 0, oth, cur, N1, N2);
+        transpose(oth, cur, N1, N2, 1);
         // data ends in `cur` (8 passes): no buffer flip
     } else {
         if (n > 1) {
@@ -601,10 +534,9 @@ static int ntt_exec(const ntt_tw *p, fe4 *cur, fe4 *oth, int inverse,
                                0, 0, cur, n, p->logn);
         }
         if (ev_mid) HIP_TRY(hipEventRecord(*ev_mid, 0));
-        const fe9 *tw = inverse ? p->d_tw_inv : p->d_tw;
         for (int s = 1; s <= p->logn; s++) {
             hipLaunchKernelGGL(k_ntt_stage, dim3(blocks_for(n / 2, 256)),
-                               dim3(256), 0, 0, cur, tw, n, p->logn, s);
+                               dim3(256), 0, 0, cur, d.tw, n, p->logn, s);
         }
         if (inverse && !coset) {
             hipLaunchKernelGGL(k_ntt_scale, dim3(blocks_for(n, 256)), dim3(256),
@@ -627,6 +559,7 @@ static int ntt_plan_run(em_ntt_plan *p, int inverse, int coset) {
     if (rc) return rc;
     if (flipped) p->cur ^= 1;
     HIP_TRY(hipEventRecord(p->ev[2], 0));
+    HIP_TRY(hipGetLastError());   // a launch the runtime refused
     HIP_TRY(hipDeviceSynchronize());
     float ms;
     HIP_TRY(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
@@ -654,11 +587,8 @@ extern "C" int ethrex_mi355_ntt_run_coset(em_ntt_plan *p, int inverse) {
 
 extern "C" int ethrex_mi355_ntt_download(em_ntt_plan *p, uint8_t *elems32) {
     if (!p || !elems32) return EM_ERR_INPUT;
-    fe4 *cur = p->cur ? p->d_work : p->d_data;
-    hipLaunchKernelGGL(k_fr_to_be, dim3(blocks_for(p->n, 256)), dim3(256), 0, 0,
-                       cur, p->d_bytes, p->n);
-    HIP_TRY(hipMemcpy(elems32, p->d_bytes, p->n * 32, hipMemcpyDeviceToHost));
-    return EM_OK;
+    return fr_download_be(elems32, p->n, p->cur ? p->d_work : p->d_data,
+                          p->d_bytes);
 }
 
 extern "C" int ethrex_mi355_ntt_last_times(em_ntt_plan *p, double times_ms[3]) {
@@ -669,16 +599,27 @@ extern "C" int ethrex_mi355_ntt_last_times(em_ntt_plan *p, double times_ms[3]) {
 
 // ============================ one-shot NTT ============================
 
-extern "C" int ethrex_mi355_bn254_fr_ntt(uint8_t *elems32, size_t n, int inverse) {
+static int ntt_oneshot(uint8_t *elems32, size_t n, int inverse, int coset) {
     if (!elems32 || n == 0) return EM_ERR_INPUT;
     em_ntt_plan *p = nullptr;
     int rc = ethrex_mi355_ntt_plan_create(n, &p);
     if (rc) return rc;
     rc = ethrex_mi355_ntt_upload(p, elems32);
-    if (!rc) rc = ethrex_mi355_ntt_run(p, inverse);
+    if (!rc)
+        rc = coset ? ethrex_mi355_ntt_run_coset(p, inverse)
+                   : ethrex_mi355_ntt_run(p, inverse);
     if (!rc) rc = ethrex_mi355_ntt_download(p, elems32);
     ethrex_mi355_ntt_plan_destroy(p);
     return rc;
+}
+
+extern "C" int ethrex_mi355_bn254_fr_ntt(uint8_t *elems32, size_t n, int inverse) {
+    return ntt_oneshot(elems32, n, inverse, 0);
+}
+
+extern "C" int ethrex_mi355_bn254_fr_coset_ntt(uint8_t *elems32, size_t n,
+                                               int inverse) {
+    return ntt_oneshot(elems32, n, inverse, 1);
 }
 
 // device pointer to the CURRENT data buffer (packed fe4m Montgomery) — the
@@ -691,19 +632,6 @@ extern "C" int ethrex_mi355_ntt_device_data(em_ntt_plan *p, const void **ptr,
     *ptr = p->cur ? p->d_work : p->d_data;
     if (n) *n = p->n;
     return EM_OK;
-}
-
-extern "C" int ethrex_mi355_bn254_fr_coset_ntt(uint8_t *elems32, size_t n,
-                                               int inverse) {
-    if (!elems32 || n == 0) return EM_ERR_INPUT;
-    em_ntt_plan *p = nullptr;
-    int rc = ethrex_mi355_ntt_plan_create(n, &p);
-    if (rc) return rc;
-    rc = ethrex_mi355_ntt_upload(p, elems32);
-    if (!rc) rc = ethrex_mi355_ntt_run_coset(p, inverse);
-    if (!rc) rc = ethrex_mi355_ntt_download(p, elems32);
-    ethrex_mi355_ntt_plan_destroy(p);
-    return rc;
 }
 
 // ===================== quotient polynomial (Groth16 H) =====================
@@ -772,17 +700,11 @@ extern "C" int ethrex_mi355_quot_plan_destroy(em_quot_plan *q) {
 extern "C" int ethrex_mi355_quot_upload(em_quot_plan *q, int which,
                                         const uint8_t *elems32) {
     if (!q || !elems32 || which < 0 || which > 2) return EM_ERR_INPUT;
-    size_t n = q->tw.n;
-    uint8_t *stage = (uint8_t *)q->buf[q->work];
     q->loaded[which] = false;
     if (which == 0) q->has_h = false;
-    HIP_TRY(hipMemset(q->d_err, 0, 4));
-    HIP_TRY(hipMemcpy(stage, elems32, n * 32, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_fr_from_be, dim3(blocks_for(n, 256)), dim3(256), 0, 0,
-                       stage, q->buf[q->slot[which]], n, q->d_err);
-    uint32_t err;
-    HIP_TRY(hipMemcpy(&err, q->d_err, 4, hipMemcpyDeviceToHost));
-    if (err) return EM_ERR_INPUT;
+    int rc = fr_upload_be(elems32, q->tw.n, (uint8_t *)q->buf[q->work],
+                          q->buf[q->slot[which]], q->d_err);
+    if (rc) return rc;
     q->loaded[which] = true;
     return EM_OK;
 }
@@ -860,12 +782,8 @@ extern "C" int ethrex_mi355_quot_run(em_quot_plan *q) {
 
 extern "C" int ethrex_mi355_quot_download(em_quot_plan *q, uint8_t *elems32) {
     if (!q || !elems32 || !q->has_h) return EM_ERR_INPUT;
-    size_t n = q->tw.n;
-    uint8_t *stage = (uint8_t *)q->buf[q->work];
-    hipLaunchKernelGGL(k_fr_to_be, dim3(blocks_for(n, 256)), dim3(256), 0, 0,
-                       q->buf[q->slot[0]], stage, n);
-    HIP_TRY(hipMemcpy(elems32, stage, n * 32, hipMemcpyDeviceToHost));
-    return EM_OK;
+    return fr_download_be(elems32, q->tw.n, q->buf[q->slot[0]],
+                          (uint8_t *)q->buf[q->work]);
 }
 
 extern "C" int ethrex_mi355_quot_device_data(em_quot_plan *q, const void **ptr,

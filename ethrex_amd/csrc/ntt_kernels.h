@@ -24,10 +24,10 @@
 // Two row-kernel shapes, A/B-measured (profiles/r02_summary.md):
 // radix-2^2 at 1024 threads (4 waves/SIMD; the DEFAULT — occupancy hides
 // the LDS+mul latency best) and radix-2^3 at 512 threads (3 DIT stages
-// per LDS round trip, 1/3 the LDS traffic; EM_NTT_R8 selects it).  Both
-// use a SKEWED LDS layout — the bit-reversed load scatter otherwise hits
-// one bank group wave-wide — and dynamic LDS so 2048-element rows run 2
-// blocks/CU.
+// per LDS round trip, 1/3 the LDS traffic; EM_NTT_R8 selects it).
+// EM_NTT_TD sets the radix-2^2 block size.  Both use a SKEWED LDS layout
+// — the bit-reversed load scatter otherwise hits one bank group wave-wide
+// — and dynamic LDS so 2048-element rows run 2 blocks/CU.
 //
 // Two paths (selected in api_ntt.hip):
 //   13 <= logn <= 24: four-step fused (3 tiled transposes + 2 LDS row-NTT
@@ -82,17 +82,18 @@ __global__ void k_fr_to_be(const fe4 *__restrict__ in, uint8_t *__restrict__ out
     o[3] = __builtin_bswap64(w[0]);
 }
 
-// ---- twiddle generation ----
-// row tables (fe9, small): tw[j] = w^j, j in [0, count); w2k[k] = w^(2^k).
-__global__ void k_gen_twiddles(fe9 *__restrict__ tw, size_t count,
-                               const fe9 *__restrict__ w2k, int bits) {
+// ---- twiddle / power-table generation ----
+// out[j] = s * b^j, j < count (fe9 Montgomery); b2k[k] = b^(2^k), k < bits.
+// The row twiddle tables are b = w, s = 1; the coset tables b = g^(+-2^k).
+__global__ void k_gen_pow(fe9 *__restrict__ out, size_t count,
+                          const fe9 *__restrict__ b2k, int bits, fe9 s) {
     size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= count) return;
-    fe9 acc = fe9_load(bn254::FR9_ONE);
+    fe9 acc = s;
     size_t e = j;
     for (int k = 0; k < bits && e; k++, e >>= 1)
-        if (e & 1) acc = mont_mul9<Fr9T>(acc, w2k[k]);
-    tw[j] = acc;
+        if (e & 1) acc = mont_mul9<Fr9T>(acc, b2k[k]);
+    out[j] = acc;
 }
 
 // reordered P1 table (fe4m, streamed): TW2[c*M + k] = w^(k*c), c < rows,
@@ -157,159 +158,148 @@ k_transpose_fe4(const fe4 *__restrict__ src, fe4 *__restrict__ dst,
         dst[base + (size_t)(c0 + dy) * R + r0 + tx] = tile[tx][dy];
 }
 
-// one row NTT of length M = 2^logM fully in LDS (fe9: 4096*36 B = 144 KiB).
-// 512 threads x 8 elements; radix-2^3 rounds (three DIT stages in
-// registers per LDS round trip), radix-2^2 / radix-2 tail for logM % 3.
+// ---- row NTT of length M = 2^logM, fully in LDS ----
+// (fe9: 4096*36 B = 144 KiB, dynamic: (M + M/64) slots, so 2048-element
+// rows run 2 blocks/CU (73 KiB) instead of being pinned at the 4096-row
+// footprint.)  One body, ntt_row_body<RADIX_LOG2, COSET>, built from the
+// pieces below; the block strides over the row, so any block size works.
 // tw2 (fe4m, may be null): output k scaled by TW2[c*M + k], c = blockIdx
 // & cmask; scale (fe9, may be null): iNTT 1/n factor.
+//
 // skewed LDS indexing: physical slot = i + (i >> 6).  The bit-reversed
 // load scatter otherwise lands a whole wave on one bank group (rev of
 // consecutive i strides 2048 elements; 9*2048 dwords = 0 mod 64 banks
 // = a 64-way conflict); with the skew, lane l's slot moves by
 // rev6(l)*65 -> 9*rev6(l) mod 64, a permutation of the banks.
-#define EM_SK(i) ((i) + ((i) >> 6))
-// COSET (compile-time; the row kernels' bodies are shared templates so the
-// plain COSET = 0 kernels compile to the code they were before):
+__device__ __forceinline__ constexpr uint32_t row_sk(uint32_t i) {
+    return i + (i >> 6);
+}
+
+// COSET (compile-time, so the plain COSET = 0 kernels carry none of it):
 //   0  plain transform; cs_elem / cs_row unused.
 //   1  coset forward, P1: element i is multiplied by cs_elem[i] = (g^N2)^i
 //      on load and output row c additionally by cs_row[c] = g^c.
 //   2  coset inverse, P2: output k of row k1 is multiplied by
 //      cs_row[k1] = g^(-k1) n^-1 and cs_elem[k] = (g^(-N1))^k (scale unused).
 // Both tables are fe9, at most 4096 entries, shared by all rows.
+
+// bit-reversed load of one row into the skewed LDS row
 template <int COSET>
 __device__ __forceinline__ void
-ntt_row_body(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
-             const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
-             uint32_t cmask, const fe9 *__restrict__ cs_elem,
-             const fe9 *__restrict__ cs_row) {
-    // dynamic LDS, (M + M/64) fe9 slots: 2048-element rows then run 2
-    // blocks/CU (73 KiB) instead of being pinned at the 4096-row footprint
-    extern __shared__ fe9 smem[];
+row_load(fe9 *smem, const fe4 *row, int logM,
+         const fe9 *__restrict__ cs_elem) {
     const uint32_t M = 1u << logM;
-    fe4 *row = data + (size_t)blockIdx.x * M;
     for (uint32_t i = threadIdx.x; i < M; i += blockDim.x) {
         uint32_t j = __brev(i) >> (32 - logM);
         if constexpr (COSET == 1)
-            smem[EM_SK(j)] = mont_mul9<Fr9T>(fe4m_unpack(row[i]), cs_elem[i]);
+            smem[row_sk(j)] = mont_mul9<Fr9T>(fe4m_unpack(row[i]), cs_elem[i]);
         else
-            smem[EM_SK(j)] = fe4m_unpack(row[i]);
+            smem[row_sk(j)] = fe4m_unpack(row[i]);
     }
     __syncthreads();
-    int s = 1;
-    // radix-2^3 rounds: stages s, s+1, s+2 on 8 register-resident elements
-    for (; s + 2 <= logM; s += 3) {
-        uint32_t q = 1u << (s - 1);
-        for (uint32_t t = threadIdx.x; t < (M >> 3); t += blockDim.x) {
-            uint32_t j = t & (q - 1);
-            uint32_t base = ((t >> (s - 1)) << (s + 2)) + j;
-            fe9 e0 = smem[EM_SK(base)];
-            fe9 e1 = smem[EM_SK(base + q)];
-            fe9 e2 = smem[EM_SK(base + 2 * q)];
-            fe9 e3 = smem[EM_SK(base + 3 * q)];
-            fe9 e4 = smem[EM_SK(base + 4 * q)];
-            fe9 e5 = smem[EM_SK(base + 5 * q)];
-            fe9 e6 = smem[EM_SK(base + 6 * q)];
-            fe9 e7 = smem[EM_SK(base + 7 * q)];
-            // stage s: stride-q pairs, shared twiddle
-            fe9 w0 = tw_row[j << (logM - s)];
-            fe9 v;
-            v = mont_mul9<Fr9T>(e1, w0);
-            e1 = subm9<Fr9T>(e0, v);
-            e0 = add9_n<Fr9T>(e0, v);
-            v = mont_mul9<Fr9T>(e3, w0);
-            e3 = subm9<Fr9T>(e2, v);
-            e2 = add9_n<Fr9T>(e2, v);
-            v = mont_mul9<Fr9T>(e5, w0);
-            e5 = subm9<Fr9T>(e4, v);
-            e4 = add9_n<Fr9T>(e4, v);
-            v = mont_mul9<Fr9T>(e7, w0);
-            e7 = subm9<Fr9T>(e6, v);
-            e6 = add9_n<Fr9T>(e6, v);
-            // stage s+1: stride-2q pairs, twiddles at j and j+q
-            fe9 wa = tw_row[j << (logM - s - 1)];
-            fe9 wb = tw_row[(j + q) << (logM - s - 1)];
-            v = mont_mul9<Fr9T>(e2, wa);
-            e2 = subm9<Fr9T>(e0, v);
-            e0 = add9_n<Fr9T>(e0, v);
-            v = mont_mul9<Fr9T>(e3, wb);
-            e3 = subm9<Fr9T>(e1, v);
-            e1 = add9_n<Fr9T>(e1, v);
-            v = mont_mul9<Fr9T>(e6, wa);
-            e6 = subm9<Fr9T>(e4, v);
-            e4 = add9_n<Fr9T>(e4, v);
-            v = mont_mul9<Fr9T>(e7, wb);
-            e7 = subm9<Fr9T>(e5, v);
-            e5 = add9_n<Fr9T>(e5, v);
-            // stage s+2: stride-4q pairs, twiddles at j, j+q, j+2q, j+3q
-            fe9 w4a = tw_row[j << (logM - s - 2)];
-            fe9 w4b = tw_row[(j + q) << (logM - s - 2)];
-            fe9 w4c = tw_row[(j + 2 * q) << (logM - s - 2)];
-            fe9 w4d = tw_row[(j + 3 * q) << (logM - s - 2)];
-            v = mont_mul9<Fr9T>(e4, w4a);
-            e4 = subm9<Fr9T>(e0, v);
-            e0 = add9_n<Fr9T>(e0, v);
-            v = mont_mul9<Fr9T>(e5, w4b);
-            e5 = subm9<Fr9T>(e1, v);
-            e1 = add9_n<Fr9T>(e1, v);
-            v = mont_mul9<Fr9T>(e6, w4c);
-            e6 = subm9<Fr9T>(e2, v);
-            e2 = add9_n<Fr9T>(e2, v);
-            v = mont_mul9<Fr9T>(e7, w4d);
-            e7 = subm9<Fr9T>(e3, v);
-            e3 = add9_n<Fr9T>(e3, v);
-            smem[EM_SK(base)] = e0;
-            smem[EM_SK(base + q)] = e1;
-            smem[EM_SK(base + 2 * q)] = e2;
-            smem[EM_SK(base + 3 * q)] = e3;
-            smem[EM_SK(base + 4 * q)] = e4;
-            smem[EM_SK(base + 5 * q)] = e5;
-            smem[EM_SK(base + 6 * q)] = e6;
-            smem[EM_SK(base + 7 * q)] = e7;
-        }
-        __syncthreads();
+}
+
+// radix-2 DIT butterfly: (a, b) <- (a + b*w, a - b*w)
+__device__ __forceinline__ void row_bfly(fe9 &a, fe9 &b, const fe9 &w) {
+    fe9 v = mont_mul9<Fr9T>(b, w);
+    b = subm9<Fr9T>(a, v);
+    a = add9_n<Fr9T>(a, v);
+}
+
+// radix-2^3 round: stages s, s+1, s+2 on 8 register-resident elements
+__device__ __forceinline__ void
+row_round8(fe9 *smem, const fe9 *__restrict__ tw_row, int logM, int s) {
+    const uint32_t M = 1u << logM, q = 1u << (s - 1);
+    for (uint32_t t = threadIdx.x; t < (M >> 3); t += blockDim.x) {
+        uint32_t j = t & (q - 1);
+        uint32_t base = ((t >> (s - 1)) << (s + 2)) + j;
+        fe9 e[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8; k++) e[k] = smem[row_sk(base + k * q)];
+        // stage s: stride-q pairs, shared twiddle
+        fe9 w0 = tw_row[j << (logM - s)];
+        row_bfly(e[0], e[1], w0);
+        row_bfly(e[2], e[3], w0);
+        row_bfly(e[4], e[5], w0);
+        row_bfly(e[6], e[7], w0);
+        // stage s+1: stride-2q pairs, twiddles at j and j+q
+        fe9 wa = tw_row[j << (logM - s - 1)];
+        fe9 wb = tw_row[(j + q) << (logM - s - 1)];
+        row_bfly(e[0], e[2], wa);
+        row_bfly(e[1], e[3], wb);
+        row_bfly(e[4], e[6], wa);
+        row_bfly(e[5], e[7], wb);
+        // stage s+2: stride-4q pairs, twiddles at j, j+q, j+2q, j+3q
+        fe9 w4a = tw_row[j << (logM - s - 2)];
+        fe9 w4b = tw_row[(j + q) << (logM - s - 2)];
+        fe9 w4c = tw_row[(j + 2 * q) << (logM - s - 2)];
+        fe9 w4d = tw_row[(j + 3 * q) << (logM - s - 2)];
+        row_bfly(e[0], e[4], w4a);
+        row_bfly(e[1], e[5], w4b);
+        row_bfly(e[2], e[6], w4c);
+        row_bfly(e[3], e[7], w4d);
+#pragma unroll
+        for (uint32_t k = 0; k < 8; k++) smem[row_sk(base + k * q)] = e[k];
     }
-    // radix-2^2 tail (logM % 3 == 2)
-    for (; s + 1 <= logM; s += 2) {
-        uint32_t q = 1u << (s - 1);
-        for (uint32_t t = threadIdx.x; t < (M >> 2); t += blockDim.x) {
-            uint32_t j = t & (q - 1);
-            uint32_t idx = ((t >> (s - 1)) << (s + 1)) + j;
-            fe9 w1 = tw_row[j << (logM - s)];
-            fe9 a = smem[EM_SK(idx)];
-            fe9 b = mont_mul9<Fr9T>(smem[EM_SK(idx + q)], w1);
-            fe9 c = smem[EM_SK(idx + 2 * q)];
-            fe9 d = mont_mul9<Fr9T>(smem[EM_SK(idx + 3 * q)], w1);
-            fe9 t0 = add9_n<Fr9T>(a, b);
-            fe9 t1 = subm9<Fr9T>(a, b);
-            fe9 t2 = add9_n<Fr9T>(c, d);
-            fe9 t3 = subm9<Fr9T>(c, d);
-            fe9 u2 = mont_mul9<Fr9T>(t2, tw_row[j << (logM - s - 1)]);
-            fe9 u3 = mont_mul9<Fr9T>(t3, tw_row[(j + q) << (logM - s - 1)]);
-            smem[EM_SK(idx)] = add9_n<Fr9T>(t0, u2);
-            smem[EM_SK(idx + 2 * q)] = subm9<Fr9T>(t0, u2);
-            smem[EM_SK(idx + q)] = add9_n<Fr9T>(t1, u3);
-            smem[EM_SK(idx + 3 * q)] = subm9<Fr9T>(t1, u3);
-        }
-        __syncthreads();
+    __syncthreads();
+}
+
+// radix-2^2 round: stages s, s+1 on 4 elements
+__device__ __forceinline__ void
+row_round4(fe9 *smem, const fe9 *__restrict__ tw_row, int logM, int s) {
+    const uint32_t M = 1u << logM, q = 1u << (s - 1);
+    for (uint32_t t = threadIdx.x; t < (M >> 2); t += blockDim.x) {
+        uint32_t j = t & (q - 1);
+        uint32_t idx = ((t >> (s - 1)) << (s + 1)) + j;
+        fe9 w1 = tw_row[j << (logM - s)];
+        fe9 a = smem[row_sk(idx)];
+        fe9 b = mont_mul9<Fr9T>(smem[row_sk(idx + q)], w1);
+        fe9 c = smem[row_sk(idx + 2 * q)];
+        fe9 d = mont_mul9<Fr9T>(smem[row_sk(idx + 3 * q)], w1);
+        fe9 t0 = add9_n<Fr9T>(a, b);
+        fe9 t1 = subm9<Fr9T>(a, b);
+        fe9 t2 = add9_n<Fr9T>(c, d);
+        fe9 t3 = subm9<Fr9T>(c, d);
+        fe9 u2 = mont_mul9<Fr9T>(t2, tw_row[j << (logM - s - 1)]);
+        fe9 u3 = mont_mul9<Fr9T>(t3, tw_row[(j + q) << (logM - s - 1)]);
+        smem[row_sk(idx)] = add9_n<Fr9T>(t0, u2);
+        smem[row_sk(idx + 2 * q)] = subm9<Fr9T>(t0, u2);
+        smem[row_sk(idx + q)] = add9_n<Fr9T>(t1, u3);
+        smem[row_sk(idx + 3 * q)] = subm9<Fr9T>(t1, u3);
     }
-    // radix-2 tail (logM % 3 == 1)
-    for (; s <= logM; s++) {
-        uint32_t half = 1u << (s - 1);
-        for (uint32_t t = threadIdx.x; t < (M >> 1); t += blockDim.x) {
-            uint32_t j = t & (half - 1);
-            uint32_t idx = ((t >> (s - 1)) << s) + j;
-            fe9 u = smem[EM_SK(idx)];
-            fe9 v = mont_mul9<Fr9T>(smem[EM_SK(idx + half)], tw_row[j << (logM - s)]);
-            smem[EM_SK(idx)] = add9_n<Fr9T>(u, v);
-            smem[EM_SK(idx + half)] = subm9<Fr9T>(u, v);
-        }
-        __syncthreads();
+    __syncthreads();
+}
+
+// radix-2 round: stage s
+__device__ __forceinline__ void
+row_round2(fe9 *smem, const fe9 *__restrict__ tw_row, int logM, int s) {
+    const uint32_t M = 1u << logM, half = 1u << (s - 1);
+    for (uint32_t t = threadIdx.x; t < (M >> 1); t += blockDim.x) {
+        uint32_t j = t & (half - 1);
+        uint32_t idx = ((t >> (s - 1)) << s) + j;
+        fe9 u = smem[row_sk(idx)];
+        fe9 v = mont_mul9<Fr9T>(smem[row_sk(idx + half)],
+                                tw_row[j << (logM - s)]);
+        smem[row_sk(idx)] = add9_n<Fr9T>(u, v);
+        smem[row_sk(idx + half)] = subm9<Fr9T>(u, v);
     }
+    __syncthreads();
+}
+
+// store epilogue: natural order, with the TW2 / 1/n (COSET = 0) or the
+// coset (COSET = 1, 2) output factors
+template <int COSET>
+__device__ __forceinline__ void
+row_store(const fe9 *smem, fe4 *row, int logM,
+          const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
+          uint32_t cmask, const fe9 *__restrict__ cs_elem,
+          const fe9 *__restrict__ cs_row) {
+    const uint32_t M = 1u << logM;
     uint64_t c = blockIdx.x & cmask;
     const fe4 *t2row = tw2 ? tw2 + (size_t)c * M : nullptr;
     if constexpr (COSET == 0) {
         for (uint32_t k = threadIdx.x; k < M; k += blockDim.x) {
-            fe9 x = smem[EM_SK(k)];
+            fe9 x = smem[row_sk(k)];
             if (t2row) x = mont_mul9<Fr9T>(x, fe4m_unpack(t2row[k]));
             if (scale) x = mont_mul9<Fr9T>(x, *scale);
             row[k] = fe4m_pack(x);
@@ -317,7 +307,7 @@ ntt_row_body(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
     } else {
         const fe9 rowc = cs_row[c];
         for (uint32_t k = threadIdx.x; k < M; k += blockDim.x) {
-            fe9 x = mont_mul9<Fr9T>(smem[EM_SK(k)], rowc);
+            fe9 x = mont_mul9<Fr9T>(smem[row_sk(k)], rowc);
             if constexpr (COSET == 1)
                 x = mont_mul9<Fr9T>(x, fe4m_unpack(t2row[k]));
             else
@@ -327,14 +317,47 @@ ntt_row_body(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
     }
 }
 
+// RADIX_LOG2 = 3: radix-2^3 rounds (three DIT stages per LDS round trip),
+// then a radix-2^2 / radix-2 tail for logM % 3.  RADIX_LOG2 = 2: radix-2^2
+// rounds and a radix-2 tail — 1.5x the LDS round trips, but 4 elements per
+// thread, so it runs at 1024 threads and more waves/SIMD.
+template <int RADIX_LOG2, int COSET>
+__device__ __forceinline__ void
+ntt_row_body(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
+             const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
+             uint32_t cmask, const fe9 *__restrict__ cs_elem,
+             const fe9 *__restrict__ cs_row) {
+    static_assert(RADIX_LOG2 == 3 || RADIX_LOG2 == 2, "row radix");
+    static_assert(COSET >= 0 && COSET <= 2, "coset mode");
+    extern __shared__ fe9 smem[];
+    fe4 *row = data + (size_t)blockIdx.x * (1u << logM);
+    row_load<COSET>(smem, row, logM, cs_elem);
+    int s = 1;
+    if constexpr (RADIX_LOG2 == 3)
+        for (; s + 2 <= logM; s += 3) row_round8(smem, tw_row, logM, s);
+    for (; s + 1 <= logM; s += 2) row_round4(smem, tw_row, logM, s);
+    for (; s <= logM; s++) row_round2(smem, tw_row, logM, s);
+    row_store<COSET>(smem, row, logM, tw2, scale, cmask, cs_elem, cs_row);
+}
+
+// The six entry points.  k_ntt_row4*: radix-2^2, the default, at 1024
+// threads (EM_NTT_TD sets another block size); k_ntt_row*: radix-2^3 at
+// 512 threads, selected by EM_NTT_R8.  The _coset kernels take COSET = 1
+// or 2 (tw2 is required for COSET = 1).
 __global__ void __launch_bounds__(512)
 k_ntt_row(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
           const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
           uint32_t cmask = 0xffffffffu) {
-    ntt_row_body<0>(data, logM, tw_row, tw2, scale, cmask, nullptr, nullptr);
+    ntt_row_body<3, 0>(data, logM, tw_row, tw2, scale, cmask, nullptr, nullptr);
 }
 
-// coset instantiations (see COSET above); tw2 is required for COSET = 1
+__global__ void __launch_bounds__(1024)
+k_ntt_row4(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
+           const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
+           uint32_t cmask) {
+    ntt_row_body<2, 0>(data, logM, tw_row, tw2, scale, cmask, nullptr, nullptr);
+}
+
 template <int COSET>
 __global__ void __launch_bounds__(512)
 k_ntt_row_coset(fe4 *__restrict__ data, int logM,
@@ -342,99 +365,10 @@ k_ntt_row_coset(fe4 *__restrict__ data, int logM,
                 const fe9 *__restrict__ cs_elem,
                 const fe9 *__restrict__ cs_row) {
     static_assert(COSET == 1 || COSET == 2, "coset mode");
-    ntt_row_body<COSET>(data, logM, tw_row, tw2, nullptr, 0xffffffffu, cs_elem,
-                        cs_row);
+    ntt_row_body<3, COSET>(data, logM, tw_row, tw2, nullptr, 0xffffffffu,
+                           cs_elem, cs_row);
 }
 
-
-// radix-2^2 row variant (A/B occupancy experiment, EM_NTT_R4): 4 elements
-// per thread per round trip, launchable at 512/768/1024 threads — more
-// waves/SIMD than the radix-2^3 shape at the cost of 1.5x the LDS round
-// trips.  Same skewed layout and IO as k_ntt_row.
-template <int COSET>
-__device__ __forceinline__ void
-ntt_row4_body(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
-              const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
-              uint32_t cmask, const fe9 *__restrict__ cs_elem,
-              const fe9 *__restrict__ cs_row) {
-    extern __shared__ fe9 smem[];
-    const uint32_t M = 1u << logM;
-    fe4 *row = data + (size_t)blockIdx.x * M;
-    for (uint32_t i = threadIdx.x; i < M; i += blockDim.x) {
-        uint32_t j = __brev(i) >> (32 - logM);
-        if constexpr (COSET == 1)
-            smem[EM_SK(j)] = mont_mul9<Fr9T>(fe4m_unpack(row[i]), cs_elem[i]);
-        else
-            smem[EM_SK(j)] = fe4m_unpack(row[i]);
-    }
-    __syncthreads();
-    int s = 1;
-    for (; s + 1 <= logM; s += 2) {
-        uint32_t q = 1u << (s - 1);
-        for (uint32_t t = threadIdx.x; t < (M >> 2); t += blockDim.x) {
-            uint32_t j = t & (q - 1);
-            uint32_t idx = ((t >> (s - 1)) << (s + 1)) + j;
-            fe9 w1 = tw_row[j << (logM - s)];
-            fe9 a = smem[EM_SK(idx)];
-            fe9 b = mont_mul9<Fr9T>(smem[EM_SK(idx + q)], w1);
-            fe9 c = smem[EM_SK(idx + 2 * q)];
-            fe9 d = mont_mul9<Fr9T>(smem[EM_SK(idx + 3 * q)], w1);
-            fe9 t0 = add9_n<Fr9T>(a, b);
-            fe9 t1 = subm9<Fr9T>(a, b);
-            fe9 t2 = add9_n<Fr9T>(c, d);
-            fe9 t3 = subm9<Fr9T>(c, d);
-            fe9 u2 = mont_mul9<Fr9T>(t2, tw_row[j << (logM - s - 1)]);
-            fe9 u3 = mont_mul9<Fr9T>(t3, tw_row[(j + q) << (logM - s - 1)]);
-            smem[EM_SK(idx)] = add9_n<Fr9T>(t0, u2);
-            smem[EM_SK(idx + 2 * q)] = subm9<Fr9T>(t0, u2);
-            smem[EM_SK(idx + q)] = add9_n<Fr9T>(t1, u3);
-            smem[EM_SK(idx + 3 * q)] = subm9<Fr9T>(t1, u3);
-        }
-        __syncthreads();
-    }
-    for (; s <= logM; s++) {
-        uint32_t half = 1u << (s - 1);
-        for (uint32_t t = threadIdx.x; t < (M >> 1); t += blockDim.x) {
-            uint32_t j = t & (half - 1);
-            uint32_t idx = ((t >> (s - 1)) << s) + j;
-            fe9 u = smem[EM_SK(idx)];
-            fe9 v = mont_mul9<Fr9T>(smem[EM_SK(idx + half)],
-                                    tw_row[j << (logM - s)]);
-            smem[EM_SK(idx)] = add9_n<Fr9T>(u, v);
-            smem[EM_SK(idx + half)] = subm9<Fr9T>(u, v);
-        }
-        __syncthreads();
-    }
-    uint64_t c = blockIdx.x & cmask;
-    const fe4 *t2row = tw2 ? tw2 + (size_t)c * M : nullptr;
-    if constexpr (COSET == 0) {
-        for (uint32_t k = threadIdx.x; k < M; k += blockDim.x) {
-            fe9 x = smem[EM_SK(k)];
-            if (t2row) x = mont_mul9<Fr9T>(x, fe4m_unpack(t2row[k]));
-            if (scale) x = mont_mul9<Fr9T>(x, *scale);
-            row[k] = fe4m_pack(x);
-        }
-    } else {
-        const fe9 rowc = cs_row[c];
-        for (uint32_t k = threadIdx.x; k < M; k += blockDim.x) {
-            fe9 x = mont_mul9<Fr9T>(smem[EM_SK(k)], rowc);
-            if constexpr (COSET == 1)
-                x = mont_mul9<Fr9T>(x, fe4m_unpack(t2row[k]));
-            else
-                x = mont_mul9<Fr9T>(x, cs_elem[k]);
-            row[k] = fe4m_pack(x);
-        }
-    }
-}
-
-__global__ void __launch_bounds__(1024)
-k_ntt_row4(fe4 *__restrict__ data, int logM, const fe9 *__restrict__ tw_row,
-           const fe4 *__restrict__ tw2, const fe9 *__restrict__ scale,
-           uint32_t cmask) {
-    ntt_row4_body<0>(data, logM, tw_row, tw2, scale, cmask, nullptr, nullptr);
-}
-
-// coset instantiations (see COSET above); tw2 is required for COSET = 1
 template <int COSET>
 __global__ void __launch_bounds__(1024)
 k_ntt_row4_coset(fe4 *__restrict__ data, int logM,
@@ -442,8 +376,8 @@ k_ntt_row4_coset(fe4 *__restrict__ data, int logM,
                  const fe9 *__restrict__ cs_elem,
                  const fe9 *__restrict__ cs_row) {
     static_assert(COSET == 1 || COSET == 2, "coset mode");
-    ntt_row4_body<COSET>(data, logM, tw_row, tw2, nullptr, 0xffffffffu, cs_elem,
-                         cs_row);
+    ntt_row_body<2, COSET>(data, logM, tw_row, tw2, nullptr, 0xffffffffu,
+                           cs_elem, cs_row);
 }
 
 // packed small-row NTT: 1024/M rows of length M <= 512 per block (the
@@ -496,18 +430,6 @@ __global__ void k_ntt_scale(fe4 *__restrict__ a, size_t n, int logn) {
 }
 
 // ---- coset / quotient support (DESIGN.md "Quotient polynomial") ----
-
-// out[j] = s * b^j, j < count (fe9 Montgomery); b2k[k] = b^(2^k), k < bits
-__global__ void k_gen_pow(fe9 *__restrict__ out, size_t count,
-                          const fe9 *__restrict__ b2k, int bits, fe9 s) {
-    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= count) return;
-    fe9 acc = s;
-    size_t e = j;
-    for (int k = 0; k < bits && e; k++, e >>= 1)
-        if (e & 1) acc = mont_mul9<Fr9T>(acc, b2k[k]);
-    out[j] = acc;
-}
 
 // standalone coset scale: a[i] *= hi[i >> lo_bits] * lo[i & (2^lo_bits - 1)]
 // (g^(+-i), and the 1/n of the inverse, split over two small tables)
