@@ -17,7 +17,8 @@ from .lib import (EM_OK, EM_ERR_POINT, EM_ERR_INPUT, EM_ERR_HIP,
                   g1_combine_cpu, gen_fr,
                   bls_g1_add, bls_g1_mul, bls_g1_msm, bls_g1_combine,
                   bls_gen_fr, bls_g2_add, bls_g2_mul, bls_g2_msm,
-                  BlsG2MsmPlan, keccak256_batch, KeccakPlan, last_error)
+                  BlsG2MsmPlan, bn254_g2_add, bn254_g2_mul, bn254_g2_msm,
+                  Bn254G2MsmPlan, keccak256_batch, KeccakPlan, last_error)
 
 __all__ = [
     "EM_OK", "EM_ERR_POINT", "EM_ERR_INPUT", "EM_ERR_HIP",
@@ -27,6 +28,7 @@ __all__ = [
     "g1_combine_cpu", "gen_fr",
     "bls_g1_add", "bls_g1_mul", "bls_g1_msm", "bls_g1_combine", "bls_gen_fr",
     "bls_g2_add", "bls_g2_mul", "bls_g2_msm", "BlsG2MsmPlan",
+    "bn254_g2_add", "bn254_g2_mul", "bn254_g2_msm", "Bn254G2MsmPlan",
     "keccak256_batch", "KeccakPlan",
     "last_error",
 ]

@@ -37,7 +37,7 @@ struct msm_plan_t {
     static constexpr int PB = pt_bytes<C>::AFF;  // affine point bytes
     static constexpr int JB = pt_bytes<C>::JAC;  // Jacobian partial bytes
     static constexpr int AB = PB;                // affine out bytes
-    static constexpr int SB = std::is_same_v<C, Bn254G1> ? 254 : 256;
+    static constexpr int SB = msm_curve<C>::BN_SCALARS ? 254 : 256;
     size_t n;
     int cbits;                        // window config: 8 (small) or 16
     g1aT<C> *d_pts = nullptr;
@@ -192,11 +192,20 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
     // batch-affine experiment is built for that geometry).
     if (n <= 65536)
         p->cbits = 8;
-    else if (std::is_same_v<C, Bn254G1> && std::getenv("EM_MSM_TREE") == nullptr)
+    else if (msm_curve<C>::BN_SCALARS &&
+             (msm_curve<C>::SIGNED_ONLY ||
+              std::getenv("EM_MSM_TREE") == nullptr))
         p->cbits = 17;
     else
         p->cbits = 16;
-    if (p->cbits == 17 && n >= ((size_t)1 << 30)) p->cbits = 16;  // SGN_IDX
+    if (p->cbits == 17 && n >= ((size_t)1 << 30)) {  // SGN_IDX
+        if (msm_curve<C>::SIGNED_ONLY) {
+            delete p;
+            g_last_err = "msm_plan_create: n >= 2^30 unsupported";
+            return EM_ERR_INPUT;
+        }
+        p->cbits = 16;
+    }
     int nwin, nseg_tot, npart, sort_bits;
     uint32_t nbuckets;
     auto geom = [&](auto cfg) {
@@ -375,7 +384,10 @@ static int msm_upload_points_t(msm_plan_t<C> *p, const uint8_t *points) {
     constexpr int PB = msm_plan_t<C>::PB;
     HIP_TRY(hipMemset(p->d_err, 0, 4));
     HIP_TRY(hipMemcpy(p->d_scratch, points, p->n * PB, hipMemcpyHostToDevice));
-    if constexpr (std::is_same_v<C, BlsG2>) {
+    if constexpr (msm_curve<C>::OWN_IO) {
+        msm_curve<C>::launch_parse_points(p->d_scratch, p->d_pts, p->d_inf,
+                                          p->n, p->d_err);
+    } else if constexpr (std::is_same_v<C, BlsG2>) {
         hipLaunchKernelGGL(k_bls_g2_parse_points, dim3(blocks_for(p->n, 256)),
                            dim3(256), 0, 0, p->d_scratch, p->d_pts, p->d_inf,
                            p->n, p->d_err);
@@ -395,7 +407,7 @@ static int msm_upload_points_t(msm_plan_t<C> *p, const uint8_t *points) {
         return EM_ERR_INPUT;
     }
     if (err & 4u) {
-        g_last_err = "G1 point not in subgroup";
+        g_last_err = msm_curve<C>::SUBGROUP_ERR;
         return EM_ERR_POINT;
     }
     if (err) return EM_ERR_POINT;
@@ -409,7 +421,9 @@ static int msm_gen_points_t(msm_plan_t<C> *p, uint64_t start) {
     if (!p) return EM_ERR_INPUT;
     int rc0 = msm_sync_t(p);  // drain async steps: d_pts is live on s_comp
     if (rc0) return rc0;
-    if constexpr (std::is_same_v<C, BlsG2>) {
+    if constexpr (msm_curve<C>::OWN_IO) {
+        msm_curve<C>::launch_gen_points(p->d_pts, p->d_inf, p->n, start);
+    } else if constexpr (std::is_same_v<C, BlsG2>) {
         hipLaunchKernelGGL(k_bls_g2_gen_points, dim3(blocks_for(p->n, 256)),
                            dim3(256), 0, 0, p->d_pts, p->d_inf, p->n, start);
     } else if constexpr (std::is_same_v<C, BlsG1>) {
@@ -431,7 +445,10 @@ static int msm_download_points_t(msm_plan_t<C> *p, uint8_t *out) {
     int rc0 = msm_sync_t(p);  // drain async steps: d_scratch races otherwise
     if (rc0) return rc0;
     constexpr int PB = msm_plan_t<C>::PB;
-    if constexpr (std::is_same_v<C, BlsG2>) {
+    if constexpr (msm_curve<C>::OWN_IO) {
+        msm_curve<C>::launch_points_to_be(p->d_pts, p->d_inf, p->d_scratch,
+                                          p->n);
+    } else if constexpr (std::is_same_v<C, BlsG2>) {
         hipLaunchKernelGGL(k_bls_g2_points_to_be, dim3(blocks_for(p->n, 256)),
                            dim3(256), 0, 0, p->d_pts, p->d_inf, p->d_scratch,
                            p->n);
@@ -479,7 +496,7 @@ static int msm_upload_scalars_t(msm_plan_t<C> *p, const uint8_t *scalars32) {
     int rc0 = msm_sync_t(p);
     if (rc0) return rc0;
     HIP_TRY(hipMemcpy(p->d_scratch, scalars32, p->n * 32, hipMemcpyHostToDevice));
-    if constexpr (!std::is_same_v<C, Bn254G1>) {
+    if constexpr (!msm_curve<C>::BN_SCALARS) {
         // raw 256-bit scalars, no reduction (blst SCALAR_BITS = 256)
         hipLaunchKernelGGL(k_bls_parse_scalars, dim3(blocks_for(p->n, 256)),
                            dim3(256), 0, 0, p->d_scratch, p->d_scalars, p->n);
@@ -943,16 +960,21 @@ static int msm_run_async_t(msm_plan_t<C> *p, uint8_t *out, int out_mode = 0) {
         g_last_err = "msm_run_async: points/scalars not uploaded";
         return EM_ERR_INPUT;
     }
-    if (p->fixed_base) return msm_run_async_cfg<C, CfgFB>(p, out, out_mode);
+    if constexpr (!msm_curve<C>::SIGNED_ONLY) {
+        if (p->fixed_base) return msm_run_async_cfg<C, CfgFB>(p, out, out_mode);
+    }
     if (p->cbits == 8)
         return msm_run_async_cfg<C, msm_cfg<8, msm_plan_t<C>::SB>>(p, out,
                                                                    out_mode);
-    if constexpr (std::is_same_v<C, Bn254G1>) {
+    if constexpr (msm_curve<C>::BN_SCALARS) {
         if (p->cbits == 17)
             return msm_run_async_cfg<C, CfgSg254>(p, out, out_mode);
     }
-    return msm_run_async_cfg<C, msm_cfg<16, msm_plan_t<C>::SB>>(p, out,
-                                                                out_mode);
+    if constexpr (msm_curve<C>::SIGNED_ONLY)
+        return EM_ERR_INPUT;  // unreachable: create picks 8 or 17
+    else
+        return msm_run_async_cfg<C, msm_cfg<16, msm_plan_t<C>::SB>>(p, out,
+                                                                    out_mode);
 }
 
 template <typename C>
@@ -964,13 +986,18 @@ static int msm_run_inner_t(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
     }
     int rc = msm_sync_t(p);  // drain any pipelined steps first
     if (rc) return rc;
-    if (p->fixed_base) return msm_run_cfg<C, CfgFB>(p, out, out_mode);
+    if constexpr (!msm_curve<C>::SIGNED_ONLY) {
+        if (p->fixed_base) return msm_run_cfg<C, CfgFB>(p, out, out_mode);
+    }
     if (p->cbits == 8)
         return msm_run_cfg<C, msm_cfg<8, msm_plan_t<C>::SB>>(p, out, out_mode);
-    if constexpr (std::is_same_v<C, Bn254G1>) {
+    if constexpr (msm_curve<C>::BN_SCALARS) {
         if (p->cbits == 17) return msm_run_cfg<C, CfgSg254>(p, out, out_mode);
     }
-    return msm_run_cfg<C, msm_cfg<16, msm_plan_t<C>::SB>>(p, out, out_mode);
+    if constexpr (msm_curve<C>::SIGNED_ONLY)
+        return EM_ERR_INPUT;  // unreachable: create picks 8 or 17
+    else
+        return msm_run_cfg<C, msm_cfg<16, msm_plan_t<C>::SB>>(p, out, out_mode);
 }
 
 // opaque ABI types

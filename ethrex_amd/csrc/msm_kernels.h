@@ -29,6 +29,7 @@
 // ============================================================================
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "gpu_field.h"   // fe4: Fr scalar handling
 #include "gpu_g1_9.h"    // fe9: Fq / G1 compute core
 #include "gpu_g1_9_lazy.h"  // BN254 bucket walk: lazy signed mixed add
@@ -81,6 +82,31 @@ using CfgSg254 = msm_cfg<17, 254, true>;  // BN254 large DEFAULT: signed c=17
 using CfgS254 = msm_cfg<8, 254>;       // BN254 small (n <= 2^16)
 using CfgL256 = msm_cfg<16, 256>;      // BLS large
 using CfgS256 = msm_cfg<8, 256>;       // BLS small
+
+// Per-curve decisions of the shared machinery.  The primary template states
+// what the three in-header curves do; a curve that lives in its own header
+// (BN254 G2: msm_kernels_g2_bn254.h, included by its TU only) specialises
+// it and, with OWN_IO, supplies its input-kernel launchers
+// (launch_parse_points / launch_gen_points / launch_points_to_be).
+template <typename C>
+struct msm_curve {
+    // 32-B BE scalars reduced mod the BN254 r (254 bits): k_parse_scalars,
+    // and signed c=17 windows for large n
+    static constexpr bool BN_SCALARS = std::is_same_v<C, Bn254G1>;
+    // the gather walk uses the lazy signed mixed add (gpu_g1_9_lazy.h)
+    static constexpr bool LAZY_WALK = std::is_same_v<C, Bn254G1>;
+    // every n > 65536 runs signed c=17: unsigned c=16, the fixed-base
+    // config and the EM_MSM_TREE tree are not instantiated
+    static constexpr bool SIGNED_ONLY = false;
+    static constexpr bool OWN_IO = false;
+    static constexpr const char *SUBGROUP_ERR = "G1 point not in subgroup";
+};
+
+// affine negate of the signed walk (add -P for a negative digit)
+template <typename C>
+__device__ __forceinline__ void g1a_neg_y9(g1aT<C> &p) {
+    p.y = neg9<typename C::F>(p.y);
+}
 
 // sorted-value bit layout for SIGNED configs (vals[] entries)
 constexpr uint32_t SGN_NEG = 0x80000000u;   // digit is negative: add -P
@@ -300,12 +326,13 @@ k_bucket_acc(const g1aT<C> *__restrict__ pts, const uint32_t *__restrict__ vals,
     // add so the dependent idx->point load chain overlaps the VALU work.
     uint32_t v = GATHER ? vals[lo] : 0;
     g1aT<C> p = GATHER ? pts[v & IMASK] : pts[lo];
-    // BN254 (L=9) gather walks use the lazy signed add: the accumulator
+    // BN254 G1 gather walks use the lazy signed add: the accumulator
     // lives under the looser invariant of gpu_g1_9_lazy.h, infinity rides
     // in a register flag (acc stays g1_inf9() while it is set), and the
     // bucket is tightened to norm2p once at the end.  BLS (L=14: no lazy
-    // headroom) and the tree finisher keep the g1_add_affine9 loop below.
-    if constexpr (GATHER && C::F::L == 9) {
+    // headroom), BN254 G2 (no lazy Fq2 add yet) and the tree finisher keep
+    // the g1_add_affine9 loop below.
+    if constexpr (GATHER && msm_curve<C>::LAZY_WALK) {
         bool acc_inf = true;
         for (uint32_t t = lo; t < hi; t++) {
             g1aT<C> cur = p;
@@ -331,7 +358,7 @@ k_bucket_acc(const g1aT<C> *__restrict__ pts, const uint32_t *__restrict__ vals,
         p = GATHER ? pts[v & IMASK] : pts[nxt];
         if constexpr (CFG::SIGNED) {
             if (vc & SGN_SKIP) continue;  // parked zero digit / infinity
-            if (vc & SGN_NEG) cur.y = neg9<typename C::F>(cur.y);  // add -P
+            if (vc & SGN_NEG) g1a_neg_y9<C>(cur);  // add -P
         }
         if constexpr (!GATHER) {
             // tree outputs may be the identity (P + (-P)): encoded (0,0)

@@ -613,6 +613,128 @@ class BlsG2MsmPlan:
             pass
 
 
+# ==== BN254 G2 (the Groth16 B-query; EIP-197 byte semantics) ====
+# 128-byte points x.c1||x.c0||y.c1||y.c0 (imaginary part first, canonical
+# 32-B BE coords), all-zero = identity; scalars 32-B BE reduced mod r;
+# mul/msm/upload_points enforce the r-subgroup check, add on-curve only.
+
+for _f in ("bn254_g2_add", "bn254_g2_mul", "bn254_g2_msm",
+           "bn254_g2_msm_plan_create", "bn254_g2_msm_plan_destroy",
+           "bn254_g2_msm_upload_points", "bn254_g2_msm_gen_points",
+           "bn254_g2_msm_download_points", "bn254_g2_msm_upload_scalars",
+           "bn254_g2_msm_run", "bn254_g2_msm_run_partial",
+           "bn254_g2_msm_run_async", "bn254_g2_msm_sync",
+           "bn254_g2_msm_last_times", "bn254_g2_msm_scalars_from_ntt"):
+    getattr(_lib, f"ethrex_mi355_{_f}").restype = ctypes.c_int
+
+
+def bn254_g2_add(p1: bytes, p2: bytes):
+    out = (ctypes.c_uint8 * 128)()
+    rc = _lib.ethrex_mi355_bn254_g2_add(_buf(p1), _buf(p2), out)
+    return rc, bytes(out)
+
+
+def bn254_g2_mul(point: bytes, scalar: bytes):
+    out = (ctypes.c_uint8 * 128)()
+    rc = _lib.ethrex_mi355_bn254_g2_mul(_buf(point), _buf(scalar), out)
+    return rc, bytes(out)
+
+
+def bn254_g2_msm(points: bytes, scalars: bytes, n: int):
+    out = (ctypes.c_uint8 * 128)()
+    rc = _lib.ethrex_mi355_bn254_g2_msm(_buf(points), _buf(scalars),
+                                        ctypes.c_size_t(n), out)
+    return rc, bytes(out)
+
+
+class Bn254G2MsmPlan:
+    """Device-resident BN254 G2 MSM plan (Groth16 B2 = sum w_i * B_i)."""
+
+    def __init__(self, n: int):
+        self.n = n
+        self._p = ctypes.c_void_p()
+        self._pending = []
+        _check(_lib.ethrex_mi355_bn254_g2_msm_plan_create(
+            ctypes.c_size_t(n), ctypes.byref(self._p)),
+            "bn254_g2_msm_plan_create")
+
+    def upload_points(self, points: bytes):
+        _check(_lib.ethrex_mi355_bn254_g2_msm_upload_points(self._p,
+                                                            _buf(points)),
+               "bn254_g2_msm_upload_points")
+
+    def gen_points(self, start: int = 0):
+        _check(_lib.ethrex_mi355_bn254_g2_msm_gen_points(
+            self._p, ctypes.c_uint64(start)), "bn254_g2_msm_gen_points")
+
+    def download_points(self) -> bytes:
+        out = (ctypes.c_uint8 * (128 * self.n))()
+        _check(_lib.ethrex_mi355_bn254_g2_msm_download_points(self._p, out),
+               "bn254_g2_msm_download_points")
+        return bytes(out)
+
+    def upload_scalars(self, scalars: bytes):
+        _check(_lib.ethrex_mi355_bn254_g2_msm_upload_scalars(self._p,
+                                                             _buf(scalars)),
+               "bn254_g2_msm_upload_scalars")
+
+    def scalars_from_ntt(self, ntt_plan, offset: int = 0):
+        """take this plan's n scalars from an NttPlan / QuotPlan's
+        device-resident vector at element `offset` (on device, no PCIe):
+        the witness vector feeds B2 directly"""
+        ptr, nn = ntt_plan.device_data()
+        if offset + self.n > nn:
+            raise HipCoreError(EM_ERR_INPUT,
+                               f"scalars_from_ntt: offset {offset} + n "
+                               f"{self.n} exceeds NTT size {nn}")
+        _check(_lib.ethrex_mi355_bn254_g2_msm_scalars_from_ntt(
+            self._p, ptr, ctypes.c_uint64(offset)),
+            "bn254_g2_msm_scalars_from_ntt")
+
+    def run(self) -> bytes:
+        out = (ctypes.c_uint8 * 128)()
+        _check(_lib.ethrex_mi355_bn254_g2_msm_run(self._p, out),
+               "bn254_g2_msm_run")
+        return bytes(out)
+
+    def run_partial(self) -> bytes:
+        out = (ctypes.c_uint8 * 192)()
+        _check(_lib.ethrex_mi355_bn254_g2_msm_run_partial(self._p, out),
+               "bn254_g2_msm_run_partial")
+        return bytes(out)
+
+    def run_async(self):
+        buf = (ctypes.c_uint8 * 128)()
+        _check(_lib.ethrex_mi355_bn254_g2_msm_run_async(self._p, buf),
+               "bn254_g2_msm_run_async")
+        self._pending.append(buf)
+
+    def sync(self) -> bytes:
+        _check(_lib.ethrex_mi355_bn254_g2_msm_sync(self._p),
+               "bn254_g2_msm_sync")
+        outs = [bytes(b) for b in self._pending]
+        self._pending = []
+        return outs[-1] if outs else b""
+
+    def last_times(self):
+        t = (ctypes.c_double * 5)()
+        _check(_lib.ethrex_mi355_bn254_g2_msm_last_times(self._p, t),
+               "bn254_g2_msm_last_times")
+        return {"digits_sort_ms": t[0], "bucket_acc_ms": t[1],
+                "reduce_ms": t[2], "combine_ms": t[3], "total_ms": t[4]}
+
+    def destroy(self):
+        if self._p:
+            _lib.ethrex_mi355_bn254_g2_msm_plan_destroy(self._p)
+            self._p = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
 def keccak256_batch(msgs: bytes, offsets, n: int):
     """Batched Ethereum keccak256 (one-shot, PCIe-inclusive); offsets is a
     list of n+1 byte offsets into msgs."""

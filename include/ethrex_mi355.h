@@ -299,6 +299,55 @@ int ethrex_mi355_bls_msm_last_times(em_bls_msm_plan *plan, double times_ms[5]);
 /* n elements uniform in [0, r_bls) (canonical blob field elements) */
 void ethrex_mi355_bls_gen_fr(uint64_t seed, size_t n, uint8_t *out32);
 
+/* ---- BN254 G2 (the Groth16 B-query; EIP-197 byte semantics) over
+ * Fq2 = Fq[u]/(u^2+1), twist y^2 = x^3 + 3/(9+u).
+ *   affine point, 128 B: x.c1||x.c0||y.c1||y.c0, each 32-B big-endian --
+ *     IMAGINARY part first (the opposite of the BLS c0||c1 order).
+ *     All-zero bytes are the identity, on input and output.  Coordinates
+ *     must be canonical (< p), else EM_ERR_INPUT (stricter than the G1
+ *     mod-order convention, as EIP-197 requires); off-curve: EM_ERR_POINT.
+ *   subgroup: G2 has cofactor 2p - r; mul, msm and upload_points enforce
+ *     r*P = O (else EM_ERR_POINT, last_error "G2 point not in subgroup");
+ *     add checks on-curve only.
+ *   scalars: 32-B big-endian, reduced mod r.
+ *   Jacobian partial, 192 B: X||Y||Z, each element c1||c0 canonical;
+ *     Z = 0 is the identity.
+ * Geometry: c=8 for n <= 65536, signed c=17 for every larger n
+ * (n < 2^30); EM_MSM_TREE does not apply. ---- */
+typedef struct em_bn254_g2_msm_plan em_bn254_g2_msm_plan;
+int ethrex_mi355_bn254_g2_add(const uint8_t p1[128], const uint8_t p2[128],
+                              uint8_t out[128]);
+int ethrex_mi355_bn254_g2_mul(const uint8_t point[128],
+                              const uint8_t scalar[32], uint8_t out[128]);
+int ethrex_mi355_bn254_g2_msm(const uint8_t *points128,
+                              const uint8_t *scalars32, size_t n,
+                              uint8_t out[128]);
+int ethrex_mi355_bn254_g2_msm_plan_create(size_t n,
+                                          em_bn254_g2_msm_plan **plan);
+int ethrex_mi355_bn254_g2_msm_plan_destroy(em_bn254_g2_msm_plan *plan);
+int ethrex_mi355_bn254_g2_msm_upload_points(em_bn254_g2_msm_plan *plan,
+                                            const uint8_t *points128);
+int ethrex_mi355_bn254_g2_msm_gen_points(em_bn254_g2_msm_plan *plan,
+                                         uint64_t start);
+int ethrex_mi355_bn254_g2_msm_download_points(em_bn254_g2_msm_plan *plan,
+                                              uint8_t *out128);
+int ethrex_mi355_bn254_g2_msm_upload_scalars(em_bn254_g2_msm_plan *plan,
+                                             const uint8_t *scalars32);
+int ethrex_mi355_bn254_g2_msm_run(em_bn254_g2_msm_plan *plan,
+                                  uint8_t out[128]);
+int ethrex_mi355_bn254_g2_msm_run_partial(em_bn254_g2_msm_plan *plan,
+                                          uint8_t out[192]);
+int ethrex_mi355_bn254_g2_msm_run_async(em_bn254_g2_msm_plan *plan,
+                                        uint8_t out[128]);
+int ethrex_mi355_bn254_g2_msm_sync(em_bn254_g2_msm_plan *plan);
+int ethrex_mi355_bn254_g2_msm_last_times(em_bn254_g2_msm_plan *plan,
+                                         double times_ms[5]);
+/* take the plan's n scalars from an NTT/quotient plan's device-resident
+ * vector (fe4m) at element `offset`: the witness vector feeds B2 on device */
+int ethrex_mi355_bn254_g2_msm_scalars_from_ntt(em_bn254_g2_msm_plan *plan,
+                                               const void *ntt_data,
+                                               uint64_t offset);
+
 #ifdef __cplusplus
 }
 #endif
