@@ -63,6 +63,37 @@ extern "C" int ethrex_mi355_msm_last_times(em_msm_plan *p, double times_ms[5]) {
     return EM_OK;
 }
 
+// merged fixed-base mode of this plan: window bits c (0 = off: the
+// separate-window path runs), the time the last table build took and the
+// table's size
+extern "C" int ethrex_mi355_msm_fb_info(em_msm_plan *p, int *c,
+                                        double *precompute_ms,
+                                        uint64_t *table_bytes) {
+    if (!p) return EM_ERR_INPUT;
+    if (c) *c = p->fb_c;
+    if (precompute_ms) *precompute_ms = p->fb_precompute_ms;
+    if (table_bytes) *table_bytes = p->fb_table_bytes;
+    return EM_OK;
+}
+
+// rows [start, start + count) of window w of the fixed-base table, as
+// 64-B BE affine points (parity tests: row i must be 2^(c*w) * P_i)
+extern "C" int ethrex_mi355_msm_download_fb_rows(em_msm_plan *p, int w,
+                                                 size_t start, size_t count,
+                                                 uint8_t *out64) {
+    if (!p || !out64 || !p->fb_c || !p->have_points || w < 0 ||
+        w >= (254 + p->fb_c - 1) / p->fb_c || count == 0 || start >= p->n ||
+        count > p->n - start)
+        return EM_ERR_INPUT;
+    int rc0 = msm_sync_t((msm_plan_t<Bn254G1> *)p);
+    if (rc0) return rc0;
+    hipLaunchKernelGGL(k_points_to_be, dim3(blocks_for(count, 256)), dim3(256),
+                       0, 0, p->d_pts_ext + (size_t)w * p->n + start,
+                       p->d_inf + start, p->d_scratch, count);
+    HIP_TRY(hipMemcpy(out64, p->d_scratch, count * 64, hipMemcpyDeviceToHost));
+    return EM_OK;
+}
+
 // combine Jacobian partials reusing the plan's buffers (no per-call
 // hipMalloc: the N>1 exchange runs this every step)
 extern "C" int ethrex_mi355_msm_combine(em_msm_plan *p,

@@ -43,6 +43,16 @@ struct msm_plan_t {
     g1aT<C> *d_pts = nullptr;
     g1aT<C> *d_pts_ext = nullptr;     // fixed-base table (FB_NWIN * n)
     bool fixed_base = false;
+    // merged fixed-base mode (large BN254 G1, msm_fb_recode.h): window bits
+    // c, or 0 = off.  d_pts_ext then holds NWIN_REAL * n table rows, built
+    // by upload_points / gen_points; d_offsets/d_sched are per walk slot.
+    int fb_c = 0;
+    uint32_t fb_chunk = 0;            // L: most entries one walk slot takes
+    int fb_len_bits = 0;              // L < 2^fb_len_bits (schedule sort)
+    double fb_precompute_ms = 0;
+    uint64_t fb_table_bytes = 0;
+    uint32_t *d_fb_boff = nullptr;    // per-bucket offsets (NBUCKETS + 1)
+    g1jT<C> *d_fb_slots = nullptr;    // per-slot walk results (NSLOT)
     uint8_t *d_inf = nullptr;
     fe4 *d_scalars = nullptr;
     uint8_t *d_scratch = nullptr;     // PB*n bytes: point/scalar byte staging
@@ -132,6 +142,8 @@ static int msm_destroy_t(msm_plan_t<C> *p) {
     }
     (void)hipFree(p->d_pts);
     (void)hipFree(p->d_pts_ext);
+    (void)hipFree(p->d_fb_boff);
+    (void)hipFree(p->d_fb_slots);
     (void)hipFree(p->d_inf);
     (void)hipFree(p->d_scalars);
     (void)hipFree(p->d_scratch);
@@ -176,6 +188,53 @@ static int msm_destroy_t(msm_plan_t<C> *p) {
     return EM_OK;
 }
 
+// ---- merged fixed-base mode: selection and per-c dispatch ----
+// Default on for BN254 G1 plans of n >= FBM_MIN_N when the table fits:
+// free device memory (hipMemGetInfo; EM_MSM_FB_FREE_BYTES overrides the
+// probe) must cover 1.5x the table (the table, plus the sorted pairs in
+// three copies = a third of it, plus slack) and 6 GiB for the bucket/slot
+// arrays.  EM_MSM_FB=0 forces the separate-window path, EM_MSM_FB=<c>
+// (20, 22, 24) forces the mode at any n.  Table indices ride in the sorted
+// values next to the sign bits, so NWIN_REAL * n must stay below 2^30.
+constexpr int FBM_DEFAULT_C = 22;
+constexpr size_t FBM_MIN_N = (size_t)1 << 23;
+
+template <typename FN>
+static int fbm_dispatch(int c, FN fn) {
+    switch (c) {
+    case 20: return fn(CfgFbm20{});
+    case 22: return fn(CfgFbm22{});
+    case 24: return fn(CfgFbm24{});
+    }
+    return EM_ERR_INPUT;
+}
+
+template <typename C>
+static int fbm_select(size_t n) {
+    if constexpr (!msm_curve<C>::FB_MERGED) {
+        return 0;
+    } else {
+        int c = 0;
+        if (const char *ev = std::getenv("EM_MSM_FB")) {
+            c = atoi(ev);
+            if (c != 20 && c != 22 && c != 24) return 0;
+        } else if (n >= FBM_MIN_N && std::getenv("EM_MSM_TREE") == nullptr) {
+            c = FBM_DEFAULT_C;
+        } else {
+            return 0;
+        }
+        size_t nwr = (size_t)((254 + c - 1) / c);
+        if (nwr * n >= ((size_t)1 << 30)) return 0;  // SGN_IDX
+        size_t table = nwr * n * sizeof(g1aT<C>);
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 0;
+        if (const char *fv = std::getenv("EM_MSM_FB_FREE_BYTES"))
+            free_b = (size_t)strtoull(fv, nullptr, 10);
+        if (free_b < table + table / 2 + ((size_t)6 << 30)) return 0;
+        return c;
+    }
+}
+
 template <typename C>
 static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
     if (!plan || n == 0) return EM_ERR_INPUT;
@@ -183,6 +242,19 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
     if (rc) return rc;
     auto *p = new msm_plan_t<C>();
     p->n = n;
+    p->fb_c = fbm_select<C>(n);
+    if (p->fb_c) {
+        // the table first: if it does not fit after all, run today's path
+        size_t nwr = (size_t)((254 + p->fb_c - 1) / p->fb_c);
+        p->fb_table_bytes = nwr * n * sizeof(g1aT<C>);
+        if (hipMalloc((void **)&p->d_pts_ext, p->fb_table_bytes) !=
+            hipSuccess) {
+            (void)hipGetLastError();
+            p->d_pts_ext = nullptr;
+            p->fb_table_bytes = 0;
+            p->fb_c = 0;
+        }
+    }
     // small MSMs (blob-KZG-sized) use c=8: the fixed bucket-reduction tail
     // shrinks 256x.  Large BN254 MSMs default to SIGNED c=17 (15 windows:
     // 6% fewer point adds at the same bucket count; scalars are reduced mod
@@ -226,6 +298,30 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
     // per-window sorts (n >= 2^23) carry only the 16-bit in-window id as
     // the key: 25% less sort traffic, half the key memory
     p->keys16 = n >= ((size_t)1 << 23);
+    // nsched: entries of the walk schedule (buckets; merged mode: slots)
+    size_t nsched = nbuckets;
+    if constexpr (msm_curve<C>::FB_MERGED) {
+        if (p->fb_c) {
+            fbm_dispatch(p->fb_c, [&](auto cfg) {
+                using G = decltype(cfg);
+                geom(cfg);
+                total = n * (size_t)G::NWIN_REAL;
+                nsched = G::NSLOT;
+                return 0;
+            });
+            p->keys16 = false;  // one global sort over u32 bucket ids
+            // slot length cap: 1.25x the average run, never below it (the
+            // NSLOT bound), EM_MSM_FB_CHUNK overrides for experiments
+            size_t avg = (total + nbuckets - 1) / nbuckets;
+            size_t L = (avg * 5 + 3) / 4;
+            if (const char *cv = std::getenv("EM_MSM_FB_CHUNK"))
+                L = (size_t)strtoull(cv, nullptr, 10);
+            if (L < avg) L = avg;
+            if (L < 8) L = 8;
+            p->fb_chunk = (uint32_t)L;
+            while ((L >> p->fb_len_bits) != 0) p->fb_len_bits++;
+        }
+    }
     const size_t kb = p->keys16 ? 2 : 4;
     hipError_t e = hipSuccess;
     auto mal = [&](void **ptr, size_t bytes) {
@@ -239,12 +335,24 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
     mal((void **)&p->d_vals, total * 4);
     mal((void **)&p->d_keys_out, total * kb);
     mal((void **)&p->d_vals_out, total * 4);
-    mal((void **)&p->d_offsets, ((size_t)nbuckets + 1) * 4);
-    mal((void **)&p->d_blen, (size_t)nbuckets * 4);
-    mal((void **)&p->d_blen_out, (size_t)nbuckets * 4);
-    mal((void **)&p->d_bids, (size_t)nbuckets * 4);
-    mal((void **)&p->d_sched, (size_t)nbuckets * 4);
+    mal((void **)&p->d_offsets, (nsched + 1) * 4);
+    mal((void **)&p->d_blen, nsched * 4);
+    mal((void **)&p->d_blen_out, nsched * 4);
+    mal((void **)&p->d_bids, nsched * 4);
+    mal((void **)&p->d_sched, nsched * 4);
     mal((void **)&p->d_buckets, (size_t)nbuckets * sizeof(g1jT<C>));
+    if constexpr (msm_curve<C>::FB_MERGED) if (p->fb_c) {
+        mal((void **)&p->d_fb_boff, ((size_t)nbuckets + 1) * 4);
+        mal((void **)&p->d_fb_slots, nsched * sizeof(g1jT<C>));
+        mal((void **)&p->d_cnt, ((size_t)nbuckets + 1) * 4);
+        mal((void **)&p->d_loff[0], ((size_t)nbuckets + 1) * 4);
+        mal((void **)&p->d_loff[1], ((size_t)nbuckets + 1) * 4);
+        if (e == hipSuccess)
+            e = rocprim::exclusive_scan(nullptr, p->scan_tmp_bytes, p->d_cnt,
+                                        p->d_loff[0], 0u,
+                                        (size_t)nbuckets + 1);
+        if (e == hipSuccess) e = hipMalloc(&p->d_scan_tmp, p->scan_tmp_bytes);
+    }
     mal((void **)&p->d_seg_sum, (size_t)nseg_tot * sizeof(g1jT<C>));
     mal((void **)&p->d_seg_wsum, (size_t)nseg_tot * sizeof(g1jT<C>));
     mal((void **)&p->d_partials, (size_t)npart * sizeof(g1jT<C>));
@@ -265,7 +373,7 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
         if (e == hipSuccess)
             e = rocprim::radix_sort_pairs(nullptr, tmp_len, p->d_blen,
                                           p->d_blen_out, p->d_bids, p->d_sched,
-                                          (size_t)nbuckets, 0, 32);
+                                          nsched, 0, 32);
         if (tmp_len > p->sort_tmp_bytes) p->sort_tmp_bytes = tmp_len;
         if (e == hipSuccess) e = hipMalloc(&p->d_sort_tmp, p->sort_tmp_bytes);
     }
@@ -278,7 +386,7 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
     // round-2 experiments; the product path stays XYZZ.
     if constexpr (std::is_same_v<C, Bn254G1>) {
         size_t avg = total / CfgL254::NBUCKETS;
-        if (p->cbits == 16 && avg >= 8 && e == hipSuccess &&
+        if (p->cbits == 16 && avg >= 8 && e == hipSuccess && !p->fb_c &&
             std::getenv("EM_MSM_TREE") != nullptr) {
             p->use_tree = true;
             int lg = 0;
@@ -327,8 +435,8 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
     // async pipelined path: second sort-output buffer set + streams
     mal((void **)&p->d_keys_out2, total * kb);
     mal((void **)&p->d_vals_out2, total * 4);
-    mal((void **)&p->d_offsets2, ((size_t)nbuckets + 1) * 4);
-    mal((void **)&p->d_sched2, (size_t)nbuckets * 4);
+    mal((void **)&p->d_offsets2, (nsched + 1) * 4);
+    mal((void **)&p->d_sched2, nsched * 4);
     mal((void **)&p->d_out2, (size_t)NWIN_MAX * msm_plan_t<C>::JB);
     // EQUAL-priority streams (default).  The pass-B experiment that gave
     // s_comp higher priority STARVED the low-priority sort stream: the
@@ -376,6 +484,30 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
     return EM_OK;
 }
 
+// merged fixed-base mode: (re)build T[w*n + i] = 2^(c*w) * P_i from the
+// points just loaded.  Setup work, once per point set; the time is kept
+// for last_times()/fb_info.
+template <typename C>
+static int fbm_build_table(msm_plan_t<C> *p) {
+    if constexpr (msm_curve<C>::FB_MERGED) {
+        if (!p->fb_c) return EM_OK;
+        HIP_TRY(hipEventRecord(p->ev[0], 0));
+        fbm_dispatch(p->fb_c, [&](auto cfg) {
+            using G = decltype(cfg);
+            hipLaunchKernelGGL((k_fbm_precompute<C, G>),
+                               dim3(blocks_for(p->n, 256)), dim3(256), 0, 0,
+                               p->d_pts, p->d_inf, p->n, p->d_pts_ext);
+            return 0;
+        });
+        HIP_TRY(hipEventRecord(p->ev[1], 0));
+        HIP_TRY(hipDeviceSynchronize());
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
+        p->fb_precompute_ms = ms;
+    }
+    return EM_OK;
+}
+
 template <typename C>
 static int msm_upload_points_t(msm_plan_t<C> *p, const uint8_t *points) {
     if (!p || !points) return EM_ERR_INPUT;
@@ -411,6 +543,8 @@ static int msm_upload_points_t(msm_plan_t<C> *p, const uint8_t *points) {
         return EM_ERR_POINT;
     }
     if (err) return EM_ERR_POINT;
+    int rcf = fbm_build_table(p);
+    if (rcf) return rcf;
     p->have_points = true;
     p->fixed_base = false;
     return EM_OK;
@@ -434,6 +568,8 @@ static int msm_gen_points_t(msm_plan_t<C> *p, uint64_t start) {
                            0, 0, p->d_pts, p->d_inf, p->n, start);
     }
     HIP_TRY(hipDeviceSynchronize());
+    int rcf = fbm_build_table(p);
+    if (rcf) return rcf;
     p->have_points = true;
     p->fixed_base = false;
     return EM_OK;
@@ -737,9 +873,118 @@ static int msm_sync_t(msm_plan_t<C> *p) {
         if (_e != hipSuccess) return _e;    \
     } while (0)
 
+// ---- merged fixed-base chains (CFG = msm_cfg_fbm<c, 254>) ----
+// sort chain: digits of all windows -> ONE radix sort over the c-1 id bits
+// -> bucket offsets -> runs cut into slots of <= fb_chunk entries (counts,
+// exclusive scan, refined offsets) -> length-sorted slot schedule.
+template <typename C, typename CFG>
+static hipError_t fbm_enqueue_sort_chain(msm_plan_t<C> *p, int par,
+                                         hipStream_t ss) {
+    const size_t total = p->n * (size_t)CFG::NWIN_REAL;
+    constexpr uint32_t NB = CFG::NBUCKETS, NS = CFG::NSLOT;
+    uint32_t *KO = par ? p->d_keys_out2 : p->d_keys_out;
+    uint32_t *VO = par ? p->d_vals_out2 : p->d_vals_out;
+    uint32_t *SOFF = par ? p->d_offsets2 : p->d_offsets;
+    uint32_t *SCH = par ? p->d_sched2 : p->d_sched;
+    uint32_t *COFF = p->d_loff[par];
+    hipLaunchKernelGGL((k_fbm_digits<CFG>), dim3(blocks_for(p->n, 256)),
+                       dim3(256), 0, ss, p->d_scalars, p->d_inf, p->d_keys,
+                       p->d_vals, p->n);
+    size_t tmp = p->sort_tmp_bytes;
+    EM_HT(rocprim::radix_sort_pairs(p->d_sort_tmp, tmp, p->d_keys, KO,
+                                    p->d_vals, VO, total, 0, CFG::SORT_BITS,
+                                    ss));
+    hipLaunchKernelGGL((k_offsets<CFG>), dim3(blocks_for((size_t)NB + 1, 256)),
+                       dim3(256), 0, ss, KO, total, p->d_fb_boff);
+    hipLaunchKernelGGL((k_fbm_chunk_counts<CFG>),
+                       dim3(blocks_for((size_t)NB + 1, 256)), dim3(256), 0, ss,
+                       p->d_fb_boff, p->d_cnt, p->fb_chunk);
+    size_t st = p->scan_tmp_bytes;
+    EM_HT(rocprim::exclusive_scan(p->d_scan_tmp, st, p->d_cnt, COFF, 0u,
+                                  (size_t)NB + 1, rocprim::plus<uint32_t>(),
+                                  ss));
+    hipLaunchKernelGGL((k_fbm_slot_offsets<CFG>),
+                       dim3(blocks_for((size_t)NS + 1, 256)), dim3(256), 0, ss,
+                       p->d_fb_boff, COFF, SOFF, p->fb_chunk,
+                       (uint32_t)total);
+    hipLaunchKernelGGL((k_bucket_lengths<CfgFbmWalk>), dim3(NS / 256),
+                       dim3(256), 0, ss, SOFF, p->d_blen, p->d_bids);
+    size_t tmp2 = p->sort_tmp_bytes;
+    EM_HT(rocprim::radix_sort_pairs(p->d_sort_tmp, tmp2, p->d_blen,
+                                    p->d_blen_out, p->d_bids, SCH, (size_t)NS,
+                                    0, p->fb_len_bits, ss));
+    return hipSuccess;
+}
+
+// walk: one thread per scheduled slot over the table, lazy signed add
+template <typename C, typename CFG>
+static void fbm_enqueue_walk(msm_plan_t<C> *p, int par, hipStream_t sc) {
+    uint32_t *VO = par ? p->d_vals_out2 : p->d_vals_out;
+    uint32_t *SOFF = par ? p->d_offsets2 : p->d_offsets;
+    uint32_t *SCH = par ? p->d_sched2 : p->d_sched;
+    hipLaunchKernelGGL((k_bucket_acc<C, CfgFbmWalk>),
+                       dim3(CFG::NSLOT / 256), dim3(256), 0, sc,
+                       (const g1aT<C> *)p->d_pts_ext, VO, SOFF, SCH,
+                       p->d_fb_slots, 0u);
+}
+
+// slots -> buckets, then the shared reduction at NWIN = 1
+template <typename C, typename CFG>
+static void fbm_enqueue_reduce(msm_plan_t<C> *p, int par, hipStream_t sc) {
+    uint32_t *COFF = p->d_loff[par];
+    uint8_t *DOUT = par ? p->d_out2 : p->d_out;
+    hipLaunchKernelGGL((k_fbm_combine_groups<C, CFG>),
+                       dim3(CFG::NSLOT / 256), dim3(256), 0, sc, COFF,
+                       p->d_fb_slots);
+    hipLaunchKernelGGL((k_fbm_combine_buckets<C, CFG>),
+                       dim3(blocks_for(CFG::NBUCKETS, 256)), dim3(256), 0, sc,
+                       COFF, p->d_fb_slots, p->d_buckets);
+    hipLaunchKernelGGL((k_segment_reduce<C, CFG>),
+                       dim3(blocks_for(CFG::NSEG, 256)), dim3(256), 0, sc,
+                       p->d_buckets, p->d_seg_sum, p->d_seg_wsum);
+    hipLaunchKernelGGL((k_weighted_reduce<C, CFG>),
+                       dim3(blocks_for(CFG::NSEG, CFG::RED_BLOCK)),
+                       dim3(CFG::RED_BLOCK), 0, sc, p->d_seg_sum,
+                       p->d_seg_wsum, p->d_partials);
+    hipLaunchKernelGGL((k_window_sum<C, CFG>), dim3(1), dim3(64), 0, sc,
+                       p->d_partials, p->d_windows);
+    hipLaunchKernelGGL((k_emit_windows<C, CFG>), dim3(1), dim3(64), 0, sc,
+                       p->d_windows, DOUT);
+}
+
+// sync path (run / run_partial): the same chains on the null stream with
+// the phase events of msm_run_cfg
+template <typename C, typename CFG>
+static int msm_run_fbm(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
+    HIP_TRY(hipEventRecord(p->ev[0], 0));
+    hipError_t e = fbm_enqueue_sort_chain<C, CFG>(p, 0, 0);
+    if (e != hipSuccess) return hip_fail(e, "merged fixed-base sort chain");
+    HIP_TRY(hipEventRecord(p->ev[1], 0));
+    fbm_enqueue_walk<C, CFG>(p, 0, 0);
+    HIP_TRY(hipEventRecord(p->ev[2], 0));
+    fbm_enqueue_reduce<C, CFG>(p, 0, 0);
+    HIP_TRY(hipEventRecord(p->ev[3], 0));
+    HIP_TRY(hipEventRecord(p->ev[4], 0));
+    uint8_t wire[msm_plan_t<C>::JB];
+    HIP_TRY(hipMemcpy(wire, p->d_out, msm_plan_t<C>::JB,
+                      hipMemcpyDeviceToHost));
+    host_windows_horner<C>(wire, 1, CFG::C, out, out_mode);
+    HIP_TRY(hipDeviceSynchronize());
+    const int a[5] = {0, 1, 2, 3, 0}, b[5] = {1, 2, 3, 4, 4};
+    for (int i = 0; i < 5; i++) {
+        float ms;
+        HIP_TRY(hipEventElapsedTime(&ms, p->ev[a[i]], p->ev[b[i]]));
+        p->last_ms[i] = ms;
+    }
+    return EM_OK;
+}
+
 template <typename C, typename CFG>
 static hipError_t msm_enqueue_sort_chain(msm_plan_t<C> *p, int par,
                                          hipStream_t ss) {
+    if constexpr (is_fbm<CFG>::value) {
+        return fbm_enqueue_sort_chain<C, CFG>(p, par, ss);
+    } else {
     constexpr bool FB = std::is_same_v<CFG, CfgFB>;
     size_t total = FB ? p->n * (size_t)FB_NWIN : p->n * (size_t)CFG::NWIN;
     uint32_t *KO = par ? p->d_keys_out2 : p->d_keys_out;
@@ -792,6 +1037,7 @@ static hipError_t msm_enqueue_sort_chain(msm_plan_t<C> *p, int par,
                                     p->d_blen_out, p->d_bids, SCH,
                                     (size_t)CFG::NBUCKETS, 0, 32, ss));
     return hipSuccess;
+    }
 }
 
 // compute chain: bucket walk -> reduction -> window emission.  in_graph
@@ -801,6 +1047,12 @@ template <typename C, typename CFG>
 static hipError_t msm_enqueue_comp_chain(msm_plan_t<C> *p, int par,
                                          const g1aT<C> *pts, hipStream_t sc,
                                          bool in_graph) {
+    if constexpr (is_fbm<CFG>::value) {
+        if (!in_graph) EM_HT(hipEventRecord(p->ev_walkA[par], sc));
+        fbm_enqueue_walk<C, CFG>(p, par, sc);
+        fbm_enqueue_reduce<C, CFG>(p, par, sc);
+        return hipSuccess;
+    } else {
     uint32_t *VO = par ? p->d_vals_out2 : p->d_vals_out;
     uint32_t *OFF = par ? p->d_offsets2 : p->d_offsets;
     uint32_t *SCH = par ? p->d_sched2 : p->d_sched;
@@ -850,6 +1102,7 @@ static hipError_t msm_enqueue_comp_chain(msm_plan_t<C> *p, int par,
     hipLaunchKernelGGL((k_emit_windows<C, CFG>), dim3(1), dim3(64), 0, sc,
                        p->d_windows, DOUT);
     return hipSuccess;
+    }
 }
 
 // capture one chain as a hipGraph on `st` and instantiate it
@@ -885,7 +1138,8 @@ static int msm_capture_graph(hipStream_t st, hipGraphExec_t *exec, F enqueue,
 // disables; the EM_MSM_SPLIT gate experiment implies the direct path.
 template <typename C, typename CFG>
 static int msm_run_async_cfg(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
-    constexpr bool FB = std::is_same_v<CFG, CfgFB>;
+    // both fixed-base modes gather from the table and emit one window
+    constexpr bool FB = std::is_same_v<CFG, CfgFB> || is_fbm<CFG>::value;
     const g1aT<C> *pts = FB ? p->d_pts_ext : p->d_pts;
     int par = p->apar;
     int rc = msm_deliver(p, par);  // free this parity's slots (step k-2)
@@ -960,6 +1214,12 @@ static int msm_run_async_t(msm_plan_t<C> *p, uint8_t *out, int out_mode = 0) {
         g_last_err = "msm_run_async: points/scalars not uploaded";
         return EM_ERR_INPUT;
     }
+    if constexpr (msm_curve<C>::FB_MERGED) {
+        if (p->fb_c)
+            return fbm_dispatch(p->fb_c, [&](auto cfg) {
+                return msm_run_async_cfg<C, decltype(cfg)>(p, out, out_mode);
+            });
+    }
     if constexpr (!msm_curve<C>::SIGNED_ONLY) {
         if (p->fixed_base) return msm_run_async_cfg<C, CfgFB>(p, out, out_mode);
     }
@@ -986,6 +1246,12 @@ static int msm_run_inner_t(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
     }
     int rc = msm_sync_t(p);  // drain any pipelined steps first
     if (rc) return rc;
+    if constexpr (msm_curve<C>::FB_MERGED) {
+        if (p->fb_c)
+            return fbm_dispatch(p->fb_c, [&](auto cfg) {
+                return msm_run_fbm<C, decltype(cfg)>(p, out, out_mode);
+            });
+    }
     if constexpr (!msm_curve<C>::SIGNED_ONLY) {
         if (p->fixed_base) return msm_run_cfg<C, CfgFB>(p, out, out_mode);
     }

@@ -23,6 +23,11 @@
 //      2^(CB*w) factors (Horner) at delivery, overlapped with the next
 //      pipelined step's GPU work.
 //
+// Large BN254 G1 plans (n >= 2^23, table fits) run the MERGED fixed-base
+// geometry instead (msm_fb_recode.h, k_fbm_* below): signed c=22 digits of
+// all 12 windows in one bucket space over T[w*n+i] = 2^(c*w)*P_i, one
+// global sort, runs cut into walk slots, one reduction.
+//
 // Work shape: ~NWIN*(n + 2^(IB+1)) mixed adds; HBM traffic is only the
 // gathered points + sorted pairs => VALU-bound, so there
 // is deliberately no MFMA anywhere here.
@@ -34,6 +39,7 @@
 #include "gpu_g1_9.h"    // fe9: Fq / G1 compute core
 #include "gpu_g1_9_lazy.h"  // BN254 bucket walk: lazy signed mixed add
 #include "gpu_g2.h"      // fp2: BLS12-381 G2 specializations
+#include "msm_fb_recode.h"  // merged fixed-base geometry + digit recode
 
 namespace em {
 
@@ -99,6 +105,9 @@ struct msm_curve {
     // config and the EM_MSM_TREE tree are not instantiated
     static constexpr bool SIGNED_ONLY = false;
     static constexpr bool OWN_IO = false;
+    // large MSMs may run the merged fixed-base geometry (msm_fb_recode.h):
+    // the k_fbm_* kernels are instantiated for this curve only
+    static constexpr bool FB_MERGED = std::is_same_v<C, Bn254G1>;
     static constexpr const char *SUBGROUP_ERR = "G1 point not in subgroup";
 };
 
@@ -798,6 +807,165 @@ static __global__ void k_fb_digits(const fe4 *__restrict__ scalars,
     uint32_t d = inf[i] ? 0 : msm_digit<FB_C>(scalars[i], w);
     keys[e] = d;
     vals[e] = (uint32_t)e;
+}
+
+// ---- merged fixed-base mode for large MSMs (msm_fb_recode.h: signed
+// digits, NWIN_REAL windows, one bucket space).  All templates: only a
+// curve with msm_curve<C>::FB_MERGED instantiates them. ----
+
+// the walk runs one thread per SLOT (a bucket run cut to <= L entries);
+// the slot count is a launch property, so one k_bucket_acc instantiation
+// serves every merged c (grids are exact: NSLOT is a multiple of 256)
+struct CfgFbmWalk {
+    static constexpr bool SIGNED = true;
+    static constexpr uint32_t NBUCKETS = 0xffffffffu;
+    static constexpr uint32_t DMASK = 0;
+};
+
+// T[w*n + i] = 2^(C*w) * P_i, affine norm2p.  One thread per base point
+// walks the windows incrementally (C doublings each), parks the XYZZ
+// numerators in the table slots and converts all of them with ONE
+// Montgomery-batched inversion.  Infinity entries follow the base's flag.
+template <typename C, typename CFG>
+__global__ void __launch_bounds__(256)
+k_fbm_precompute(const g1aT<C> *__restrict__ pts,
+                 const uint8_t *__restrict__ inf, size_t n,
+                 g1aT<C> *__restrict__ ext) {
+    using F = typename C::F;
+    constexpr int LN = F::L;
+    constexpr int NW = CFG::NWIN_REAL;
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    g1aT<C> base = pts[i];
+    ext[i] = base;
+    if (inf[i]) {
+        for (int w = 1; w < NW; w++) ext[(size_t)w * n + i] = base;
+        return;
+    }
+    g1jT<C> acc;
+    acc.x = base.x;
+    acc.y = base.y;
+    acc.zz = fe9_load<LN>(F::ONE);
+    acc.zzz = fe9_load<LN>(F::ONE);
+    feL<LN> zz[NW], zzz[NW], pre[NW];  // index w; [0] unused
+    feL<LN> run = fe9_load<LN>(F::ONE);
+    for (int w = 1; w < NW; w++) {
+        // odd prime order: a finite point never doubles to infinity
+        for (int d = 0; d < CFG::C; d++) acc = g1_dbl9(acc);
+        g1aT<C> num{acc.x, acc.y};
+        ext[(size_t)w * n + i] = num;
+        zz[w] = acc.zz;
+        zzz[w] = acc.zzz;
+        run = mont_mul9<F>(run, mont_mul9<F>(acc.zz, acc.zzz));
+        pre[w] = run;
+    }
+    feL<LN> inv = mont_inv9<F>(run);
+    for (int w = NW - 1; w >= 1; w--) {
+        // t = 1 / (zz_w * zzz_w); x = X*t*zzz, y = Y*t*zz (g1_to_affine9)
+        feL<LN> t = w > 1 ? mont_mul9<F>(inv, pre[w - 1]) : inv;
+        inv = mont_mul9<F>(inv, mont_mul9<F>(zz[w], zzz[w]));
+        g1aT<C> a = ext[(size_t)w * n + i];
+        a.x = fe9_csub2p<F>(mont_mul9<F>(a.x, mont_mul9<F>(t, zzz[w])));
+        a.y = fe9_csub2p<F>(mont_mul9<F>(a.y, mont_mul9<F>(t, zz[w])));
+        ext[(size_t)w * n + i] = a;
+    }
+}
+
+// signed digits of every window into the single bucket space:
+// key = |d| - 1, value = table index w*n + i with the SGN_NEG / SGN_SKIP
+// bits (NWIN_REAL * n < 2^30 is checked at plan creation)
+template <typename CFG>
+static __global__ void k_fbm_digits(const fe4 *__restrict__ scalars,
+                                    const uint8_t *__restrict__ inf,
+                                    uint32_t *__restrict__ keys,
+                                    uint32_t *__restrict__ vals, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fe4 k = scalars[i];
+    bool skip = inf[i];
+    uint32_t carry = 0;
+#pragma unroll
+    for (int w = 0; w < CFG::NWIN_REAL; w++) {
+        uint32_t neg;
+        uint32_t mag =
+            fbm_recode_step<CFG::C>(fbm_digit<CFG::C>(k.v, w), carry, neg);
+        bool sk = skip || mag == 0;
+        size_t e = (size_t)w * n + i;
+        keys[e] = sk ? 0u : mag - 1;
+        vals[e] = (uint32_t)e | (neg << 31) | (sk ? SGN_SKIP : 0u);
+    }
+    // scalars < r < 2^254: the top window (+ carry) is <= 2^TOP_BITS <=
+    // 2^(C-1), so the last step never carries out
+}
+
+// slots per bucket: max(1, ceil(len / L)); entry NBUCKETS = 0 so the
+// exclusive scan's last element is the number of slots in use
+template <typename CFG>
+static __global__ void k_fbm_chunk_counts(const uint32_t *__restrict__ boff,
+                                          uint32_t *__restrict__ cnt,
+                                          uint32_t L) {
+    uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b > CFG::NBUCKETS) return;
+    if (b == CFG::NBUCKETS) {
+        cnt[b] = 0;
+        return;
+    }
+    uint32_t len = boff[b + 1] - boff[b];
+    uint32_t c = (len + L - 1) / L;
+    cnt[b] = c ? c : 1u;
+}
+
+// refined offsets: slot coff[b] + j starts at boff[b] + j*L; the chunks
+// partition the sorted array in order, so soff[s + 1] ends slot s.  Slots
+// past the last one in use are empty (soff = total).
+template <typename CFG>
+static __global__ void k_fbm_slot_offsets(const uint32_t *__restrict__ boff,
+                                          const uint32_t *__restrict__ coff,
+                                          uint32_t *__restrict__ soff,
+                                          uint32_t L, uint32_t total) {
+    uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > CFG::NSLOT) return;
+    if (t >= coff[CFG::NBUCKETS]) soff[t] = total;
+    if (t < CFG::NBUCKETS) {
+        uint32_t lo = boff[t], s0 = coff[t], k = coff[t + 1] - s0;
+        // s0 + j < NSLOT follows from L >= total/NBUCKETS (host-checked)
+        for (uint32_t j = 0; j < k && s0 + j < CFG::NSLOT; j++)
+            soff[s0 + j] = lo + j * L;
+    }
+}
+
+// slot partials -> bucket sums, two levels so a bucket with hundreds of
+// chunks costs CGRP + chunks/CGRP serial adds instead of `chunks`.
+// level 1: the first slot of every CGRP-group of a multi-slot bucket
+// gathers its group in place (groups are disjoint slot ranges).
+template <typename C, typename CFG>
+__global__ void __launch_bounds__(256)
+k_fbm_combine_groups(const uint32_t *__restrict__ coff,
+                     g1jT<C> *__restrict__ slots) {
+    uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= coff[CFG::NBUCKETS]) return;
+    uint32_t b = bucket_of(coff, CFG::NBUCKETS, s);
+    uint32_t s0 = coff[b], s1 = coff[b + 1];
+    if (s1 - s0 < 2 || (s - s0) % CFG::CGRP != 0) return;
+    uint32_t e = s + CFG::CGRP < s1 ? s + CFG::CGRP : s1;
+    g1jT<C> acc = slots[s];
+    for (uint32_t j = s + 1; j < e; j++) acc = g1_add9(acc, slots[j]);
+    slots[s] = acc;
+}
+
+// level 2: bucket b = sum of its group leaders
+template <typename C, typename CFG>
+__global__ void __launch_bounds__(256)
+k_fbm_combine_buckets(const uint32_t *__restrict__ coff,
+                      const g1jT<C> *__restrict__ slots,
+                      g1jT<C> *__restrict__ buckets) {
+    uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= CFG::NBUCKETS) return;
+    uint32_t s0 = coff[b], s1 = coff[b + 1];
+    g1jT<C> acc = slots[s0];
+    for (uint32_t j = s0 + CFG::CGRP; j < s1; j += CFG::CGRP)
+        acc = g1_add9(acc, slots[j]);
+    buckets[b] = acc;
 }
 
 // ============================================================================

@@ -168,6 +168,7 @@ struct msm_curve<Bn254G2> {
     static constexpr bool LAZY_WALK = false;    // no lazy Fq2 mixed add yet
     static constexpr bool SIGNED_ONLY = true;   // c=8 or signed c=17 only
     static constexpr bool OWN_IO = true;
+    static constexpr bool FB_MERGED = false;    // G1 only (msm_fb_recode.h)
     static constexpr const char *SUBGROUP_ERR = "G2 point not in subgroup";
     static void launch_parse_points(const uint8_t *in, g1aQ2 *pts,
                                     uint8_t *inf, size_t n, uint32_t *err) {

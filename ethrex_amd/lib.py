@@ -31,7 +31,7 @@ for _f in ("device_count", "set_device", "bn254_g1_add", "bn254_g1_mul",
            "msm_run", "msm_run_partial", "msm_run_async", "msm_sync",
            "msm_run_partial_async", "msm_wait_one", "bn254_g1_combine_cpu",
            "msm_last_times", "msm_combine", "msm_scalars_from_ntt",
-           "ntt_device_data",
+           "msm_fb_info", "msm_download_fb_rows", "ntt_device_data",
            "ntt_plan_create", "ntt_plan_destroy", "ntt_upload", "ntt_run",
            "ntt_download", "ntt_last_times", "ntt_fill_from_digests",
            "ntt_last_fill_ms", "keccak_device_digests",
@@ -179,7 +179,37 @@ class MsmPlan:
         t = (ctypes.c_double * 5)()
         _check(_lib.ethrex_mi355_msm_last_times(self._p, t), "msm_last_times")
         return {"digits_sort_ms": t[0], "bucket_acc_ms": t[1],
-                "reduce_ms": t[2], "combine_ms": t[3], "total_ms": t[4]}
+                "reduce_ms": t[2], "combine_ms": t[3], "total_ms": t[4],
+                "fb_precompute_ms": self._fb_info()[1]}
+
+    def _fb_info(self):
+        c = ctypes.c_int(0)
+        ms = ctypes.c_double(0.0)
+        nbytes = ctypes.c_uint64(0)
+        _check(_lib.ethrex_mi355_msm_fb_info(
+            self._p, ctypes.byref(c), ctypes.byref(ms), ctypes.byref(nbytes)),
+            "msm_fb_info")
+        return c.value, ms.value, nbytes.value
+
+    @property
+    def fixed_base(self) -> int:
+        """Window bits c of the merged fixed-base mode this plan runs
+        (table of 2^(c*w) * P_i built when the points are loaded), or 0
+        when it runs the separate-window path."""
+        return self._fb_info()[0]
+
+    @property
+    def fb_table_bytes(self) -> int:
+        return self._fb_info()[2]
+
+    def download_fb_rows(self, w: int, start: int, count: int) -> bytes:
+        """Rows [start, start+count) of window w of the fixed-base table
+        as 64-byte affine points (parity tests)."""
+        out = (ctypes.c_uint8 * (64 * count))()
+        _check(_lib.ethrex_mi355_msm_download_fb_rows(
+            self._p, ctypes.c_int(w), ctypes.c_size_t(start),
+            ctypes.c_size_t(count), out), "msm_download_fb_rows")
+        return bytes(out)
 
     def run_async(self):
         """Enqueue one pipelined MSM step (sort chain of the next step

@@ -111,6 +111,17 @@ int ethrex_mi355_msm_scalars_from_ntt(em_msm_plan *plan, const void *ntt_data,
  * [0]=digits+sort, [1]=bucket accumulation, [2]=bucket reduction,
  * [3]=window combine + affine, [4]=total */
 int ethrex_mi355_msm_last_times(em_msm_plan *plan, double times_ms[5]);
+/* merged fixed-base mode (large plans, bases fixed across runs): when the
+ * table T[w*n + i] = 2^(c*w) * P_i fits, upload_points / gen_points build
+ * it and every run uses one bucket space for all windows.  *c = window
+ * bits (0: the separate-window path runs), *precompute_ms = time of the
+ * last table build (setup, outside any run), *table_bytes = table size.
+ * EM_MSM_FB=0 forces the mode off, EM_MSM_FB=20|22|24 forces it on. */
+int ethrex_mi355_msm_fb_info(em_msm_plan *plan, int *c, double *precompute_ms,
+                             uint64_t *table_bytes);
+/* rows [start, start+count) of table window w as 64 B BE affine points */
+int ethrex_mi355_msm_download_fb_rows(em_msm_plan *plan, int w, size_t start,
+                                      size_t count, uint8_t *out64);
 /* combine partials reusing the plan's device buffers (per-step exchange) */
 int ethrex_mi355_msm_combine(em_msm_plan *plan, const uint8_t *jacobians96,
                              size_t count, uint8_t out[64]);
