@@ -95,7 +95,10 @@ extern "C" int ethrex_mi355_msm_download_fb_rows(em_msm_plan *p, int w,
 }
 
 // combine Jacobian partials reusing the plan's buffers (no per-call
-// hipMalloc: the N>1 exchange runs this every step)
+// hipMalloc: the N>1 exchange runs this every step).
+// HAZARD (known, left as is): this writes sb[0].out on the null stream
+// without draining the pipeline, and s_comp is non-blocking, so a parity-0
+// async step still in flight emits its windows into the same buffer.
 extern "C" int ethrex_mi355_msm_combine(em_msm_plan *p,
                                         const uint8_t *jacobians96,
                                         size_t count, uint8_t out[64]) {
@@ -104,8 +107,8 @@ extern "C" int ethrex_mi355_msm_combine(em_msm_plan *p,
     HIP_TRY(hipMemcpy(p->d_scratch, jacobians96, 96 * count,
                       hipMemcpyHostToDevice));
     hipLaunchKernelGGL((k_g1_combine<Bn254G1>), dim3(1), dim3(64), 0, 0,
-                       p->d_scratch, count, p->d_out);
-    HIP_TRY(hipMemcpy(out, p->d_out, 64, hipMemcpyDeviceToHost));
+                       p->d_scratch, count, p->sb[0].out);
+    HIP_TRY(hipMemcpy(out, p->sb[0].out, 64, hipMemcpyDeviceToHost));
     return EM_OK;
 }
 // ============================ one-shot MSMs ============================

@@ -31,6 +31,17 @@ using namespace em;
 //   BlsG1:   96-B points (canonical + subgroup-checked), raw 256-bit scalars
 // The C ABI exposes separate opaque types (em_msm_plan / em_bls_msm_plan).
 
+// The sort chain's outputs and the emitted window records, one set per step
+// parity: the async path double-buffers them (step k+1 sorts while step k
+// walks); the sync path runs parity 0.
+struct msm_step_bufs {
+    uint32_t *keys_out = nullptr;  // sorted keys (u16 per window if keys16)
+    uint32_t *vals_out = nullptr;  // sorted point indices (+ sign bits)
+    uint32_t *offsets = nullptr;   // NBUCKETS + 1 (merged mode: per slot)
+    uint32_t *sched = nullptr;     // length-sorted bucket (slot) ids
+    uint8_t *out = nullptr;        // NWIN_MAX Jacobian window records
+};
+
 template <typename C>
 struct msm_plan_t {
     using F = typename C::F;
@@ -45,7 +56,7 @@ struct msm_plan_t {
     bool fixed_base = false;
     // merged fixed-base mode (large BN254 G1, msm_fb_recode.h): window bits
     // c, or 0 = off.  d_pts_ext then holds NWIN_REAL * n table rows, built
-    // by upload_points / gen_points; d_offsets/d_sched are per walk slot.
+    // by upload_points / gen_points; sb[].offsets/sched are per walk slot.
     int fb_c = 0;
     uint32_t fb_chunk = 0;            // L: most entries one walk slot takes
     int fb_len_bits = 0;              // L < 2^fb_len_bits (schedule sort)
@@ -58,21 +69,17 @@ struct msm_plan_t {
     uint8_t *d_scratch = nullptr;     // PB*n bytes: point/scalar byte staging
     uint32_t *d_keys = nullptr;       // 16n
     uint32_t *d_vals = nullptr;
-    uint32_t *d_keys_out = nullptr;
-    uint32_t *d_vals_out = nullptr;
+    msm_step_bufs sb[2];
     void *d_sort_tmp = nullptr;
     size_t sort_tmp_bytes = 0;
-    uint32_t *d_offsets = nullptr;    // NBUCKETS + 1
     uint32_t *d_blen = nullptr;       // bucket lengths (schedule keys)
     uint32_t *d_blen_out = nullptr;
     uint32_t *d_bids = nullptr;       // bucket ids
-    uint32_t *d_sched = nullptr;      // length-sorted bucket ids
     g1jT<C> *d_buckets = nullptr;     // NBUCKET_TOTAL
     g1jT<C> *d_seg_sum = nullptr;     // NWIN*NSEG
     g1jT<C> *d_seg_wsum = nullptr;
     g1jT<C> *d_partials = nullptr;    // NWIN*NBLK_PER_WIN
     g1jT<C> *d_windows = nullptr;     // NWIN
-    uint8_t *d_out = nullptr;         // JB
     uint32_t *d_err = nullptr;
     // batch-affine pairing tree (large BN254 MSMs only; see msm_kernels.h)
     bool use_tree = false;
@@ -91,11 +98,8 @@ struct msm_plan_t {
     // async pipelined path: the sort chain (HBM-heavy) of step k+1 runs on
     // s_sort concurrently with the compute chain (VALU-heavy bucket walk +
     // reduction) of step k on s_comp.  Sort outputs are double-buffered by
-    // step parity; depth-2 backpressure via ev_comp_done.
+    // step parity (sb[]); depth-2 backpressure via ev_comp_done.
     hipStream_t s_sort = nullptr, s_comp = nullptr;
-    uint32_t *d_keys_out2 = nullptr, *d_vals_out2 = nullptr;
-    uint32_t *d_offsets2 = nullptr, *d_sched2 = nullptr;
-    uint8_t *d_out2 = nullptr;
     uint8_t *h_out[2] = {nullptr, nullptr};   // pinned window staging
     hipEvent_t ev_sort_done[2], ev_comp_done[2];
     // per-parity hipGraphs of the sort and compute chains: one step costs
@@ -124,7 +128,7 @@ struct msm_plan_t {
     int apar = 0;
 };
 
-// d_out / h_out hold up to NWIN_MAX Jacobian window records (c=8: 32 windows)
+// sb[].out / h_out hold up to NWIN_MAX Jacobian window records (c=8: 32 windows)
 constexpr int NWIN_MAX = 32;
 
 template <typename C>
@@ -149,20 +153,15 @@ static int msm_destroy_t(msm_plan_t<C> *p) {
     (void)hipFree(p->d_scratch);
     (void)hipFree(p->d_keys);
     (void)hipFree(p->d_vals);
-    (void)hipFree(p->d_keys_out);
-    (void)hipFree(p->d_vals_out);
     (void)hipFree(p->d_sort_tmp);
-    (void)hipFree(p->d_offsets);
     (void)hipFree(p->d_blen);
     (void)hipFree(p->d_blen_out);
     (void)hipFree(p->d_bids);
-    (void)hipFree(p->d_sched);
     (void)hipFree(p->d_buckets);
     (void)hipFree(p->d_seg_sum);
     (void)hipFree(p->d_seg_wsum);
     (void)hipFree(p->d_partials);
     (void)hipFree(p->d_windows);
-    (void)hipFree(p->d_out);
     (void)hipFree(p->d_err);
     (void)hipFree(p->d_lvl[0]);
     (void)hipFree(p->d_lvl[1]);
@@ -171,11 +170,13 @@ static int msm_destroy_t(msm_plan_t<C> *p) {
     (void)hipFree(p->d_loff[1]);
     (void)hipFree(p->d_cnt);
     (void)hipFree(p->d_scan_tmp);
-    (void)hipFree(p->d_keys_out2);
-    (void)hipFree(p->d_vals_out2);
-    (void)hipFree(p->d_offsets2);
-    (void)hipFree(p->d_sched2);
-    (void)hipFree(p->d_out2);
+    for (auto &b : p->sb) {
+        (void)hipFree(b.keys_out);
+        (void)hipFree(b.vals_out);
+        (void)hipFree(b.offsets);
+        (void)hipFree(b.sched);
+        (void)hipFree(b.out);
+    }
     if (p->h_out[0]) (void)hipHostFree(p->h_out[0]);
     if (p->h_out[1]) (void)hipHostFree(p->h_out[1]);
     for (int i = 0; i < 2; i++) {
@@ -235,6 +236,27 @@ static int fbm_select(size_t n) {
     }
 }
 
+// The one config ladder: calls fn(cfg_tag) with the configuration this plan
+// runs and returns its result.  The if constexpr guards keep a curve from
+// instantiating a config (and its kernels) that it never runs.
+template <typename C, typename FN>
+static int msm_with_cfg(msm_plan_t<C> *p, FN fn) {
+    if constexpr (msm_curve<C>::FB_MERGED) {
+        if (p->fb_c) return fbm_dispatch(p->fb_c, fn);
+    }
+    if constexpr (!msm_curve<C>::SIGNED_ONLY) {
+        if (p->fixed_base) return fn(CfgFB{});
+    }
+    if (p->cbits == 8) return fn(msm_cfg<8, msm_plan_t<C>::SB>{});
+    if constexpr (msm_curve<C>::BN_SCALARS) {
+        if (p->cbits == 17) return fn(CfgSg254{});
+    }
+    if constexpr (msm_curve<C>::SIGNED_ONLY)
+        return EM_ERR_INPUT;  // unreachable: create picks 8 or 17
+    else
+        return fn(msm_cfg<16, msm_plan_t<C>::SB>{});
+}
+
 template <typename C>
 static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
     if (!plan || n == 0) return EM_ERR_INPUT;
@@ -278,49 +300,42 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
         }
         p->cbits = 16;
     }
-    int nwin, nseg_tot, npart, sort_bits;
-    uint32_t nbuckets;
-    auto geom = [&](auto cfg) {
+    // total: sorted (key, value) pairs per step; nsched: entries of the
+    // walk schedule (buckets; merged mode: slots)
+    int nwin = 0, nseg_tot = 0, npart = 0, sort_bits = 0;
+    uint32_t nbuckets = 0;
+    size_t total = 0, nsched = 0;
+    msm_with_cfg(p, [&](auto cfg) {
         using G = decltype(cfg);
         nwin = G::NWIN;
         nbuckets = G::NBUCKETS;
         nseg_tot = G::NWIN * G::NSEG;
         npart = G::NPART;
         sort_bits = G::SORT_BITS;
-    };
-    if (p->cbits == 8)
-        geom(msm_cfg<8, msm_plan_t<C>::SB>{});
-    else if (p->cbits == 17)
-        geom(CfgSg254{});
-    else
-        geom(msm_cfg<16, msm_plan_t<C>::SB>{});
-    size_t total = n * (size_t)nwin;
+        if constexpr (is_fbm<G>::value) {
+            total = n * (size_t)G::NWIN_REAL;
+            nsched = G::NSLOT;
+        } else {
+            total = n * (size_t)G::NWIN;
+            nsched = G::NBUCKETS;
+        }
+        return EM_OK;
+    });
     // per-window sorts (n >= 2^23) carry only the 16-bit in-window id as
     // the key: 25% less sort traffic, half the key memory
     p->keys16 = n >= ((size_t)1 << 23);
-    // nsched: entries of the walk schedule (buckets; merged mode: slots)
-    size_t nsched = nbuckets;
-    if constexpr (msm_curve<C>::FB_MERGED) {
-        if (p->fb_c) {
-            fbm_dispatch(p->fb_c, [&](auto cfg) {
-                using G = decltype(cfg);
-                geom(cfg);
-                total = n * (size_t)G::NWIN_REAL;
-                nsched = G::NSLOT;
-                return 0;
-            });
-            p->keys16 = false;  // one global sort over u32 bucket ids
-            // slot length cap: 1.25x the average run, never below it (the
-            // NSLOT bound), EM_MSM_FB_CHUNK overrides for experiments
-            size_t avg = (total + nbuckets - 1) / nbuckets;
-            size_t L = (avg * 5 + 3) / 4;
-            if (const char *cv = std::getenv("EM_MSM_FB_CHUNK"))
-                L = (size_t)strtoull(cv, nullptr, 10);
-            if (L < avg) L = avg;
-            if (L < 8) L = 8;
-            p->fb_chunk = (uint32_t)L;
-            while ((L >> p->fb_len_bits) != 0) p->fb_len_bits++;
-        }
+    if (p->fb_c) {
+        p->keys16 = false;  // one global sort over u32 bucket ids
+        // slot length cap: 1.25x the average run, never below it (the
+        // NSLOT bound), EM_MSM_FB_CHUNK overrides for experiments
+        size_t avg = (total + nbuckets - 1) / nbuckets;
+        size_t L = (avg * 5 + 3) / 4;
+        if (const char *cv = std::getenv("EM_MSM_FB_CHUNK"))
+            L = (size_t)strtoull(cv, nullptr, 10);
+        if (L < avg) L = avg;
+        if (L < 8) L = 8;
+        p->fb_chunk = (uint32_t)L;
+        while ((L >> p->fb_len_bits) != 0) p->fb_len_bits++;
     }
     const size_t kb = p->keys16 ? 2 : 4;
     hipError_t e = hipSuccess;
@@ -333,13 +348,16 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
     mal((void **)&p->d_scratch, n * (size_t)msm_plan_t<C>::PB);
     mal((void **)&p->d_keys, total * kb);
     mal((void **)&p->d_vals, total * 4);
-    mal((void **)&p->d_keys_out, total * kb);
-    mal((void **)&p->d_vals_out, total * 4);
-    mal((void **)&p->d_offsets, (nsched + 1) * 4);
+    for (auto &b : p->sb) {
+        mal((void **)&b.keys_out, total * kb);
+        mal((void **)&b.vals_out, total * 4);
+        mal((void **)&b.offsets, (nsched + 1) * 4);
+        mal((void **)&b.sched, nsched * 4);
+        mal((void **)&b.out, (size_t)NWIN_MAX * msm_plan_t<C>::JB);
+    }
     mal((void **)&p->d_blen, nsched * 4);
     mal((void **)&p->d_blen_out, nsched * 4);
     mal((void **)&p->d_bids, nsched * 4);
-    mal((void **)&p->d_sched, nsched * 4);
     mal((void **)&p->d_buckets, (size_t)nbuckets * sizeof(g1jT<C>));
     if constexpr (msm_curve<C>::FB_MERGED) if (p->fb_c) {
         mal((void **)&p->d_fb_boff, ((size_t)nbuckets + 1) * 4);
@@ -357,23 +375,22 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
     mal((void **)&p->d_seg_wsum, (size_t)nseg_tot * sizeof(g1jT<C>));
     mal((void **)&p->d_partials, (size_t)npart * sizeof(g1jT<C>));
     mal((void **)&p->d_windows, (size_t)nwin * sizeof(g1jT<C>));
-    mal((void **)&p->d_out, (size_t)NWIN_MAX * msm_plan_t<C>::JB);
     mal((void **)&p->d_err, 4);
     if (e == hipSuccess) {
         if (p->keys16)
             e = rocprim::radix_sort_pairs(
                 nullptr, p->sort_tmp_bytes, (const uint16_t *)p->d_keys,
-                (uint16_t *)p->d_keys_out, p->d_vals, p->d_vals_out, n, 0,
-                16);
+                (uint16_t *)p->sb[0].keys_out, p->d_vals, p->sb[0].vals_out,
+                n, 0, 16);
         else
-            e = rocprim::radix_sort_pairs(nullptr, p->sort_tmp_bytes,
-                                          p->d_keys, p->d_keys_out, p->d_vals,
-                                          p->d_vals_out, total, 0, sort_bits);
+            e = rocprim::radix_sort_pairs(
+                nullptr, p->sort_tmp_bytes, p->d_keys, p->sb[0].keys_out,
+                p->d_vals, p->sb[0].vals_out, total, 0, sort_bits);
         size_t tmp_len = 0;
         if (e == hipSuccess)
             e = rocprim::radix_sort_pairs(nullptr, tmp_len, p->d_blen,
-                                          p->d_blen_out, p->d_bids, p->d_sched,
-                                          nsched, 0, 32);
+                                          p->d_blen_out, p->d_bids,
+                                          p->sb[0].sched, nsched, 0, 32);
         if (tmp_len > p->sort_tmp_bytes) p->sort_tmp_bytes = tmp_len;
         if (e == hipSuccess) e = hipMalloc(&p->d_sort_tmp, p->sort_tmp_bytes);
     }
@@ -432,12 +449,7 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
         }
     }
     for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipEventCreate(&p->ev[i]);
-    // async pipelined path: second sort-output buffer set + streams
-    mal((void **)&p->d_keys_out2, total * kb);
-    mal((void **)&p->d_vals_out2, total * 4);
-    mal((void **)&p->d_offsets2, (nsched + 1) * 4);
-    mal((void **)&p->d_sched2, nsched * 4);
-    mal((void **)&p->d_out2, (size_t)NWIN_MAX * msm_plan_t<C>::JB);
+    // async pipelined path: streams, pinned staging and ordering events
     // EQUAL-priority streams (default).  The pass-B experiment that gave
     // s_comp higher priority STARVED the low-priority sort stream: the
     // kernel timeline showed the sorts serializing into a 4.3 ms gap
@@ -646,161 +658,6 @@ static int msm_upload_scalars_t(msm_plan_t<C> *p, const uint8_t *scalars32) {
     return EM_OK;
 }
 
-template <typename C, typename CFG>
-static int msm_run_cfg(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
-    constexpr bool FB = std::is_same_v<CFG, CfgFB>;
-    size_t total = FB ? p->n * (size_t)FB_NWIN : p->n * (size_t)CFG::NWIN;
-    const g1aT<C> *pts = FB ? p->d_pts_ext : p->d_pts;
-    HIP_TRY(hipEventRecord(p->ev[0], 0));
-    if constexpr (FB) {
-        hipLaunchKernelGGL(k_fb_digits, dim3(blocks_for(total, 256)), dim3(256),
-                           0, 0, p->d_scalars, p->d_inf, p->d_keys, p->d_vals,
-                           p->n);
-    } else if (p->keys16) {
-        hipLaunchKernelGGL((k_digits<CFG, uint16_t>),
-                           dim3(blocks_for(p->n, 256)), dim3(256), 0, 0,
-                           p->d_scalars, p->d_inf, (uint16_t *)p->d_keys,
-                           p->d_vals, p->n);
-    } else {
-        hipLaunchKernelGGL((k_digits<CFG>), dim3(blocks_for(p->n, 256)),
-                           dim3(256), 0, 0, p->d_scalars, p->d_inf, p->d_keys,
-                           p->d_vals, p->n);
-    }
-    // The window bits of a key are constant within each window's segment
-    // [w*n, (w+1)*n), so for large MSMs NWIN per-window sorts over just the
-    // digit bits replace one global sort over digit+window bits — one fewer
-    // radix pass over the full 16n pair array.  Small MSMs keep the single
-    // sort (per-call overhead dominates at small n).
-    hipError_t e = hipSuccess;
-    constexpr int DBITS = CFG::DBITS;  // per-window sort key bits
-    const int nwin = FB ? FB_NWIN : CFG::NWIN;
-    if (!FB && p->keys16) {
-        for (int w = 0; w < nwin && e == hipSuccess; w++) {
-            size_t tmp = p->sort_tmp_bytes;
-            size_t off = (size_t)w * p->n;
-            e = rocprim::radix_sort_pairs(
-                p->d_sort_tmp, tmp, (const uint16_t *)p->d_keys + off,
-                (uint16_t *)p->d_keys_out + off, p->d_vals + off,
-                p->d_vals_out + off, p->n, 0, DBITS);
-        }
-    } else {
-        size_t tmp = p->sort_tmp_bytes;
-        e = rocprim::radix_sort_pairs(p->d_sort_tmp, tmp, p->d_keys,
-                                      p->d_keys_out, p->d_vals,
-                                      p->d_vals_out, total, 0,
-                                      CFG::SORT_BITS);
-    }
-    if (e != hipSuccess) return hip_fail(e, "radix_sort_pairs");
-    if (!FB && p->keys16) {
-        hipLaunchKernelGGL((k_offsets_seg<CFG>),
-                           dim3(blocks_for((size_t)CFG::NBUCKETS + 1, 256)),
-                           dim3(256), 0, 0, (const uint16_t *)p->d_keys_out,
-                           p->n, p->d_offsets);
-    } else {
-        hipLaunchKernelGGL((k_offsets<CFG>),
-                           dim3(blocks_for((size_t)CFG::NBUCKETS + 1, 256)),
-                           dim3(256), 0, 0, p->d_keys_out, total,
-                           p->d_offsets);
-    }
-    // schedule buckets by run length (kills wave divergence in the hot kernel)
-    hipLaunchKernelGGL((k_bucket_lengths<CFG>),
-                       dim3(blocks_for(CFG::NBUCKETS, 256)), dim3(256), 0, 0,
-                       p->d_offsets, p->d_blen, p->d_bids);
-    {
-        size_t tmp2 = p->sort_tmp_bytes;
-        hipError_t e2 = rocprim::radix_sort_pairs(
-            p->d_sort_tmp, tmp2, p->d_blen, p->d_blen_out, p->d_bids,
-            p->d_sched, (size_t)CFG::NBUCKETS, 0, 32);
-        if (e2 != hipSuccess) return hip_fail(e2, "bucket length sort");
-    }
-    HIP_TRY(hipEventRecord(p->ev[1], 0));
-    bool tree_done = false;
-    if constexpr (std::is_same_v<C, Bn254G1> && !FB && CFG::C == 16) {
-        if (p->use_tree) {
-            // batch-affine pairing tree, then XYZZ cleanup of the short tails
-            constexpr uint32_t NB = CFG::NBUCKETS;
-            uint32_t *o_in = p->d_offsets;
-            size_t bound = total;
-            for (int l = 0; l < p->tree_levels; l++) {
-                uint32_t *o_out = p->d_loff[l & 1];
-                hipLaunchKernelGGL(k_pair_counts,
-                                   dim3(blocks_for((size_t)NB + 1, 256)),
-                                   dim3(256), 0, 0, o_in, p->d_cnt, NB,
-                                   CFG::DMASK, l == 0 ? 1 : 0);
-                size_t st = p->scan_tmp_bytes;
-                hipError_t es = rocprim::exclusive_scan(
-                    p->d_scan_tmp, st, p->d_cnt, o_out, 0u, (size_t)NB + 1);
-                if (es != hipSuccess) return hip_fail(es, "pair scan");
-                size_t pbound = bound / 2 + NB;
-                size_t nthreads = (pbound + PAIR_K - 1) / PAIR_K;
-                g1aT<C> *dst = p->d_lvl[l & 1];
-                uint32_t cap =
-                    (uint32_t)(total / 2 + CFG::NBUCKETS + 1);
-                if (l == 0) {
-                    hipLaunchKernelGGL((k_pair_level<C, true>),
-                                       dim3(blocks_for(nthreads, 256)),
-                                       dim3(256), 0, 0, p->d_pts,
-                                       p->d_vals_out, o_in, o_out, p->d_aux,
-                                       cap, dst, NB);
-                } else {
-                    hipLaunchKernelGGL((k_pair_level<C, false>),
-                                       dim3(blocks_for(nthreads, 256)),
-                                       dim3(256), 0, 0, p->d_lvl[(l & 1) ^ 1],
-                                       nullptr, o_in, o_out, p->d_aux, cap,
-                                       dst, NB);
-                }
-                o_in = o_out;
-                bound = pbound;
-            }
-            hipLaunchKernelGGL((k_bucket_acc<C, CFG, false>),
-                               dim3(blocks_for(CFG::NBUCKETS, 256)), dim3(256),
-                               0, 0, p->d_lvl[(p->tree_levels - 1) & 1],
-                               nullptr, o_in, p->d_sched, p->d_buckets);
-            tree_done = true;
-        }
-    }
-    if (!tree_done) {
-        hipLaunchKernelGGL((k_bucket_acc<C, CFG>),
-                           dim3(blocks_for(CFG::NBUCKETS, 256)), dim3(256), 0,
-                           0, pts, p->d_vals_out, p->d_offsets, p->d_sched,
-                           p->d_buckets);
-    }
-    HIP_TRY(hipEventRecord(p->ev[2], 0));
-    hipLaunchKernelGGL((k_segment_reduce<C, CFG>),
-                       dim3(blocks_for(CFG::NWIN * CFG::NSEG, 256)), dim3(256),
-                       0, 0, p->d_buckets, p->d_seg_sum, p->d_seg_wsum);
-    hipLaunchKernelGGL((k_weighted_reduce<C, CFG>),
-                       dim3(blocks_for(CFG::NWIN * CFG::NSEG, CFG::RED_BLOCK)),
-                       dim3(CFG::RED_BLOCK), 0, 0, p->d_seg_sum, p->d_seg_wsum,
-                       p->d_partials);
-    hipLaunchKernelGGL((k_window_sum<C, CFG>), dim3(CFG::NWIN), dim3(64), 0, 0,
-                       p->d_partials, p->d_windows);
-    HIP_TRY(hipEventRecord(p->ev[3], 0));
-    constexpr int NW = FB ? 1 : CFG::NWIN;
-    hipLaunchKernelGGL((k_emit_windows<C, CFG>), dim3(1), dim3(64), 0, 0,
-                       p->d_windows, p->d_out);
-    HIP_TRY(hipEventRecord(p->ev[4], 0));
-    {
-        uint8_t wire[NWIN_MAX * msm_plan_t<C>::JB];
-        HIP_TRY(hipMemcpy(wire, p->d_out, (size_t)NW * msm_plan_t<C>::JB,
-                          hipMemcpyDeviceToHost));
-        host_windows_horner<C>(wire, NW, CFG::C, out, out_mode);
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    float ms;
-    HIP_TRY(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
-    p->last_ms[0] = ms;
-    HIP_TRY(hipEventElapsedTime(&ms, p->ev[1], p->ev[2]));
-    p->last_ms[1] = ms;
-    HIP_TRY(hipEventElapsedTime(&ms, p->ev[2], p->ev[3]));
-    p->last_ms[2] = ms;
-    HIP_TRY(hipEventElapsedTime(&ms, p->ev[3], p->ev[4]));
-    p->last_ms[3] = ms;
-    HIP_TRY(hipEventElapsedTime(&ms, p->ev[0], p->ev[4]));
-    p->last_ms[4] = ms;
-    return EM_OK;
-}
-
 // HOST window combine: fold the 2^(C*w) window factors over the nwin
 // UNSCALED Jacobian window records with a Horner pass
 //   acc = W_{n-1}; repeat { acc = 2^C * acc + W_w }  (C doublings + 1 add)
@@ -865,111 +722,272 @@ static int msm_sync_t(msm_plan_t<C> *p) {
     return msm_deliver(p, p->apar);
 }
 
-// ---- pipelined-step chain enqueue helpers (shared by the direct path
-// and the hipGraph capture below; pure kernel/rocPRIM nodes) ----
+// ======================= the MSM step, in four stages =======================
+// sort chain -> walk -> reduce -> emit.  Each stage only enqueues kernels
+// and rocPRIM calls on the stream it is given, reading and writing the step
+// buffers of one parity (p->sb[par], p->d_loff[par]), so the same code runs
+// directly on a stream and under hipGraph capture.  Event records belong to
+// the callers: msm_run_sync_cfg (run / run_partial: parity 0 on the null
+// stream, phase events between the stages) and msm_run_async_cfg (two
+// streams, per-parity graphs).  CFG is a window config (msm_cfg), the blob
+// fixed-base config (CfgFB) or a merged fixed-base config (msm_cfg_fbm).
 #define EM_HT(call)                         \
     do {                                    \
         hipError_t _e = (call);             \
         if (_e != hipSuccess) return _e;    \
     } while (0)
 
-// ---- merged fixed-base chains (CFG = msm_cfg_fbm<c, 254>) ----
-// sort chain: digits of all windows -> ONE radix sort over the c-1 id bits
-// -> bucket offsets -> runs cut into slots of <= fb_chunk entries (counts,
-// exclusive scan, refined offsets) -> length-sorted slot schedule.
+// the points the walk gathers from: both fixed-base modes read the table
 template <typename C, typename CFG>
-static hipError_t fbm_enqueue_sort_chain(msm_plan_t<C> *p, int par,
-                                         hipStream_t ss) {
-    const size_t total = p->n * (size_t)CFG::NWIN_REAL;
-    constexpr uint32_t NB = CFG::NBUCKETS, NS = CFG::NSLOT;
-    uint32_t *KO = par ? p->d_keys_out2 : p->d_keys_out;
-    uint32_t *VO = par ? p->d_vals_out2 : p->d_vals_out;
-    uint32_t *SOFF = par ? p->d_offsets2 : p->d_offsets;
-    uint32_t *SCH = par ? p->d_sched2 : p->d_sched;
-    uint32_t *COFF = p->d_loff[par];
-    hipLaunchKernelGGL((k_fbm_digits<CFG>), dim3(blocks_for(p->n, 256)),
-                       dim3(256), 0, ss, p->d_scalars, p->d_inf, p->d_keys,
-                       p->d_vals, p->n);
+static const g1aT<C> *msm_walk_pts(const msm_plan_t<C> *p) {
+    constexpr bool TABLE = std::is_same_v<CFG, CfgFB> || is_fbm<CFG>::value;
+    return TABLE ? p->d_pts_ext : p->d_pts;
+}
+
+// EM_MSM_SPLIT=<pct> (experiment, async direct path only): the walk launches
+// as two segments and the next step's sort chain waits for the first
+static int msm_split_pct() {
+    static int pct = std::getenv("EM_MSM_SPLIT")
+                         ? atoi(std::getenv("EM_MSM_SPLIT"))
+                         : 0;
+    return pct;
+}
+
+// Stage 1, sort chain: scalar digits -> radix sort by bucket -> bucket
+// offsets -> length-sorted walk schedule (kills wave divergence in the walk).
+template <typename C, typename CFG>
+static hipError_t msm_enqueue_sort_chain(msm_plan_t<C> *p, int par,
+                                         hipStream_t st) {
+    const msm_step_bufs &b = p->sb[par];
     size_t tmp = p->sort_tmp_bytes;
-    EM_HT(rocprim::radix_sort_pairs(p->d_sort_tmp, tmp, p->d_keys, KO,
-                                    p->d_vals, VO, total, 0, CFG::SORT_BITS,
-                                    ss));
-    hipLaunchKernelGGL((k_offsets<CFG>), dim3(blocks_for((size_t)NB + 1, 256)),
-                       dim3(256), 0, ss, KO, total, p->d_fb_boff);
-    hipLaunchKernelGGL((k_fbm_chunk_counts<CFG>),
-                       dim3(blocks_for((size_t)NB + 1, 256)), dim3(256), 0, ss,
-                       p->d_fb_boff, p->d_cnt, p->fb_chunk);
-    size_t st = p->scan_tmp_bytes;
-    EM_HT(rocprim::exclusive_scan(p->d_scan_tmp, st, p->d_cnt, COFF, 0u,
-                                  (size_t)NB + 1, rocprim::plus<uint32_t>(),
-                                  ss));
-    hipLaunchKernelGGL((k_fbm_slot_offsets<CFG>),
-                       dim3(blocks_for((size_t)NS + 1, 256)), dim3(256), 0, ss,
-                       p->d_fb_boff, COFF, SOFF, p->fb_chunk,
-                       (uint32_t)total);
-    hipLaunchKernelGGL((k_bucket_lengths<CfgFbmWalk>), dim3(NS / 256),
-                       dim3(256), 0, ss, SOFF, p->d_blen, p->d_bids);
-    size_t tmp2 = p->sort_tmp_bytes;
-    EM_HT(rocprim::radix_sort_pairs(p->d_sort_tmp, tmp2, p->d_blen,
-                                    p->d_blen_out, p->d_bids, SCH, (size_t)NS,
-                                    0, p->fb_len_bits, ss));
+    if constexpr (is_fbm<CFG>::value) {
+        // merged fixed-base: digits of all windows -> ONE radix sort over
+        // the c-1 id bits -> bucket offsets -> runs cut into slots of <=
+        // fb_chunk entries (counts, exclusive scan, refined offsets)
+        const size_t total = p->n * (size_t)CFG::NWIN_REAL;
+        constexpr uint32_t NB = CFG::NBUCKETS, NS = CFG::NSLOT;
+        uint32_t *coff = p->d_loff[par];
+        hipLaunchKernelGGL((k_fbm_digits<CFG>), dim3(blocks_for(p->n, 256)),
+                           dim3(256), 0, st, p->d_scalars, p->d_inf,
+                           p->d_keys, p->d_vals, p->n);
+        EM_HT(rocprim::radix_sort_pairs(p->d_sort_tmp, tmp, p->d_keys,
+                                        b.keys_out, p->d_vals, b.vals_out,
+                                        total, 0, CFG::SORT_BITS, st));
+        hipLaunchKernelGGL((k_offsets<CFG>),
+                           dim3(blocks_for((size_t)NB + 1, 256)), dim3(256), 0,
+                           st, b.keys_out, total, p->d_fb_boff);
+        hipLaunchKernelGGL((k_fbm_chunk_counts<CFG>),
+                           dim3(blocks_for((size_t)NB + 1, 256)), dim3(256), 0,
+                           st, p->d_fb_boff, p->d_cnt, p->fb_chunk);
+        size_t stmp = p->scan_tmp_bytes;
+        EM_HT(rocprim::exclusive_scan(p->d_scan_tmp, stmp, p->d_cnt, coff, 0u,
+                                      (size_t)NB + 1,
+                                      rocprim::plus<uint32_t>(), st));
+        hipLaunchKernelGGL((k_fbm_slot_offsets<CFG>),
+                           dim3(blocks_for((size_t)NS + 1, 256)), dim3(256), 0,
+                           st, p->d_fb_boff, coff, b.offsets, p->fb_chunk,
+                           (uint32_t)total);
+        hipLaunchKernelGGL((k_bucket_lengths<CfgFbmWalk>), dim3(NS / 256),
+                           dim3(256), 0, st, b.offsets, p->d_blen, p->d_bids);
+        tmp = p->sort_tmp_bytes;
+        EM_HT(rocprim::radix_sort_pairs(p->d_sort_tmp, tmp, p->d_blen,
+                                        p->d_blen_out, p->d_bids, b.sched,
+                                        (size_t)NS, 0, p->fb_len_bits, st));
+    } else {
+        constexpr bool FB = std::is_same_v<CFG, CfgFB>;
+        const size_t total = p->n * (size_t)(FB ? FB_NWIN : CFG::NWIN);
+        const bool k16 = !FB && p->keys16;
+        if constexpr (FB) {
+            hipLaunchKernelGGL(k_fb_digits, dim3(blocks_for(total, 256)),
+                               dim3(256), 0, st, p->d_scalars, p->d_inf,
+                               p->d_keys, p->d_vals, p->n);
+        } else if (p->keys16) {
+            hipLaunchKernelGGL((k_digits<CFG, uint16_t>),
+                               dim3(blocks_for(p->n, 256)), dim3(256), 0, st,
+                               p->d_scalars, p->d_inf, (uint16_t *)p->d_keys,
+                               p->d_vals, p->n);
+        } else {
+            hipLaunchKernelGGL((k_digits<CFG>), dim3(blocks_for(p->n, 256)),
+                               dim3(256), 0, st, p->d_scalars, p->d_inf,
+                               p->d_keys, p->d_vals, p->n);
+        }
+        // The window bits of a key are constant within each window's segment
+        // [w*n, (w+1)*n), so for large MSMs NWIN per-window sorts over just
+        // the digit bits replace one global sort over digit+window bits — one
+        // fewer radix pass over the full pair array.  Small MSMs keep the
+        // single sort (per-call overhead dominates at small n).
+        if (k16) {
+            for (int w = 0; w < CFG::NWIN; w++) {
+                tmp = p->sort_tmp_bytes;
+                size_t off = (size_t)w * p->n;
+                EM_HT(rocprim::radix_sort_pairs(
+                    p->d_sort_tmp, tmp, (const uint16_t *)p->d_keys + off,
+                    (uint16_t *)b.keys_out + off, p->d_vals + off,
+                    b.vals_out + off, p->n, 0, CFG::DBITS, st));
+            }
+            hipLaunchKernelGGL(
+                (k_offsets_seg<CFG>),
+                dim3(blocks_for((size_t)CFG::NBUCKETS + 1, 256)), dim3(256), 0,
+                st, (const uint16_t *)b.keys_out, p->n, b.offsets);
+        } else {
+            EM_HT(rocprim::radix_sort_pairs(p->d_sort_tmp, tmp, p->d_keys,
+                                            b.keys_out, p->d_vals, b.vals_out,
+                                            total, 0, CFG::SORT_BITS, st));
+            hipLaunchKernelGGL(
+                (k_offsets<CFG>),
+                dim3(blocks_for((size_t)CFG::NBUCKETS + 1, 256)), dim3(256), 0,
+                st, b.keys_out, total, b.offsets);
+        }
+        hipLaunchKernelGGL((k_bucket_lengths<CFG>),
+                           dim3(blocks_for(CFG::NBUCKETS, 256)), dim3(256), 0,
+                           st, b.offsets, p->d_blen, p->d_bids);
+        tmp = p->sort_tmp_bytes;
+        EM_HT(rocprim::radix_sort_pairs(p->d_sort_tmp, tmp, p->d_blen,
+                                        p->d_blen_out, p->d_bids, b.sched,
+                                        (size_t)CFG::NBUCKETS, 0, 32, st));
+    }
     return hipSuccess;
 }
 
-// walk: one thread per scheduled slot over the table, lazy signed add
+// Stage 2, walk: one thread per scheduled bucket (merged mode: per slot of
+// the table), XYZZ accumulation with the lazy signed add.  `mid` is the
+// EM_MSM_SPLIT experiment: when set, the window walk launches as two
+// segments with `mid` recorded between them (after the walk if the split
+// point degenerates); it is never set under capture.
 template <typename C, typename CFG>
-static void fbm_enqueue_walk(msm_plan_t<C> *p, int par, hipStream_t sc) {
-    uint32_t *VO = par ? p->d_vals_out2 : p->d_vals_out;
-    uint32_t *SOFF = par ? p->d_offsets2 : p->d_offsets;
-    uint32_t *SCH = par ? p->d_sched2 : p->d_sched;
-    hipLaunchKernelGGL((k_bucket_acc<C, CfgFbmWalk>),
-                       dim3(CFG::NSLOT / 256), dim3(256), 0, sc,
-                       (const g1aT<C> *)p->d_pts_ext, VO, SOFF, SCH,
-                       p->d_fb_slots, 0u);
+static hipError_t msm_enqueue_walk(msm_plan_t<C> *p, int par, hipStream_t st,
+                                   hipEvent_t mid = nullptr) {
+    const msm_step_bufs &b = p->sb[par];
+    const g1aT<C> *pts = msm_walk_pts<C, CFG>(p);
+    if constexpr (is_fbm<CFG>::value) {
+        hipLaunchKernelGGL((k_bucket_acc<C, CfgFbmWalk>),
+                           dim3(CFG::NSLOT / 256), dim3(256), 0, st, pts,
+                           b.vals_out, b.offsets, b.sched, p->d_fb_slots, 0u);
+    } else {
+        constexpr uint32_t NB = CFG::NBUCKETS;
+        auto walk = [&](uint32_t count, uint32_t base) {
+            hipLaunchKernelGGL((k_bucket_acc<C, CFG>),
+                               dim3(blocks_for(count, 256)), dim3(256), 0, st,
+                               pts, b.vals_out, b.offsets, b.sched,
+                               p->d_buckets, base);
+        };
+        uint32_t head = NB;
+        if (mid) {
+            uint32_t pct = (uint32_t)msm_split_pct();
+            uint32_t cut = (uint32_t)(((uint64_t)NB * pct) / 100) / 256 * 256;
+            if (cut != 0 && cut < NB) head = cut;
+        }
+        walk(head, 0u);
+        if (mid) EM_HT(hipEventRecord(mid, st));
+        if (head < NB) walk(NB - head, head);
+    }
+    return hipSuccess;
 }
 
-// slots -> buckets, then the shared reduction at NWIN = 1
+// Stage 2, alternate (EM_MSM_TREE experiment; sync path, BN254 G1 unsigned
+// c=16 only): batch-affine pairing tree over the sorted runs, then the XYZZ
+// walk over the last level cleans up the short tails.
 template <typename C, typename CFG>
-static void fbm_enqueue_reduce(msm_plan_t<C> *p, int par, hipStream_t sc) {
-    uint32_t *COFF = p->d_loff[par];
-    uint8_t *DOUT = par ? p->d_out2 : p->d_out;
-    hipLaunchKernelGGL((k_fbm_combine_groups<C, CFG>),
-                       dim3(CFG::NSLOT / 256), dim3(256), 0, sc, COFF,
-                       p->d_fb_slots);
-    hipLaunchKernelGGL((k_fbm_combine_buckets<C, CFG>),
-                       dim3(blocks_for(CFG::NBUCKETS, 256)), dim3(256), 0, sc,
-                       COFF, p->d_fb_slots, p->d_buckets);
+static hipError_t msm_enqueue_tree_walk(msm_plan_t<C> *p, int par,
+                                        hipStream_t st) {
+    const msm_step_bufs &b = p->sb[par];
+    constexpr uint32_t NB = CFG::NBUCKETS;
+    const size_t total = p->n * (size_t)CFG::NWIN;
+    const uint32_t cap = (uint32_t)(total / 2 + NB + 1);
+    const uint32_t *o_in = b.offsets;
+    size_t bound = total;
+    for (int l = 0; l < p->tree_levels; l++) {
+        uint32_t *o_out = p->d_loff[l & 1];
+        hipLaunchKernelGGL(k_pair_counts, dim3(blocks_for((size_t)NB + 1, 256)),
+                           dim3(256), 0, st, o_in, p->d_cnt, NB, CFG::DMASK,
+                           l == 0 ? 1 : 0);
+        size_t stmp = p->scan_tmp_bytes;
+        EM_HT(rocprim::exclusive_scan(p->d_scan_tmp, stmp, p->d_cnt, o_out, 0u,
+                                      (size_t)NB + 1,
+                                      rocprim::plus<uint32_t>(), st));
+        size_t pbound = bound / 2 + NB;
+        size_t nthreads = (pbound + PAIR_K - 1) / PAIR_K;
+        g1aT<C> *dst = p->d_lvl[l & 1];
+        if (l == 0) {
+            hipLaunchKernelGGL((k_pair_level<C, true>),
+                               dim3(blocks_for(nthreads, 256)), dim3(256), 0,
+                               st, p->d_pts, b.vals_out, o_in, o_out, p->d_aux,
+                               cap, dst, NB);
+        } else {
+            hipLaunchKernelGGL((k_pair_level<C, false>),
+                               dim3(blocks_for(nthreads, 256)), dim3(256), 0,
+                               st, p->d_lvl[(l & 1) ^ 1], nullptr, o_in, o_out,
+                               p->d_aux, cap, dst, NB);
+        }
+        o_in = o_out;
+        bound = pbound;
+    }
+    hipLaunchKernelGGL((k_bucket_acc<C, CFG, false>),
+                       dim3(blocks_for(NB, 256)), dim3(256), 0, st,
+                       p->d_lvl[(p->tree_levels - 1) & 1], nullptr, o_in,
+                       b.sched, p->d_buckets);
+    return hipSuccess;
+}
+
+// Stage 3, reduce: buckets -> per-window sums (merged mode first folds the
+// walk's slots back into buckets; both fixed-base modes reduce NWIN = 1)
+template <typename C, typename CFG>
+static void msm_enqueue_reduce(msm_plan_t<C> *p, int par, hipStream_t st) {
+    if constexpr (is_fbm<CFG>::value) {
+        hipLaunchKernelGGL((k_fbm_combine_groups<C, CFG>),
+                           dim3(CFG::NSLOT / 256), dim3(256), 0, st,
+                           p->d_loff[par], p->d_fb_slots);
+        hipLaunchKernelGGL((k_fbm_combine_buckets<C, CFG>),
+                           dim3(blocks_for(CFG::NBUCKETS, 256)), dim3(256), 0,
+                           st, p->d_loff[par], p->d_fb_slots, p->d_buckets);
+    }
     hipLaunchKernelGGL((k_segment_reduce<C, CFG>),
-                       dim3(blocks_for(CFG::NSEG, 256)), dim3(256), 0, sc,
-                       p->d_buckets, p->d_seg_sum, p->d_seg_wsum);
+                       dim3(blocks_for(CFG::NWIN * CFG::NSEG, 256)), dim3(256),
+                       0, st, p->d_buckets, p->d_seg_sum, p->d_seg_wsum);
     hipLaunchKernelGGL((k_weighted_reduce<C, CFG>),
-                       dim3(blocks_for(CFG::NSEG, CFG::RED_BLOCK)),
-                       dim3(CFG::RED_BLOCK), 0, sc, p->d_seg_sum,
+                       dim3(blocks_for(CFG::NWIN * CFG::NSEG, CFG::RED_BLOCK)),
+                       dim3(CFG::RED_BLOCK), 0, st, p->d_seg_sum,
                        p->d_seg_wsum, p->d_partials);
-    hipLaunchKernelGGL((k_window_sum<C, CFG>), dim3(1), dim3(64), 0, sc,
-                       p->d_partials, p->d_windows);
-    hipLaunchKernelGGL((k_emit_windows<C, CFG>), dim3(1), dim3(64), 0, sc,
-                       p->d_windows, DOUT);
+    hipLaunchKernelGGL((k_window_sum<C, CFG>), dim3(CFG::NWIN), dim3(64), 0,
+                       st, p->d_partials, p->d_windows);
 }
 
-// sync path (run / run_partial): the same chains on the null stream with
-// the phase events of msm_run_cfg
+// Stage 4, emit: the CFG::NWIN unscaled window sums as Jacobian wire
+// records for the host Horner
 template <typename C, typename CFG>
-static int msm_run_fbm(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
+static void msm_enqueue_emit(msm_plan_t<C> *p, int par, hipStream_t st) {
+    hipLaunchKernelGGL((k_emit_windows<C, CFG>), dim3(1), dim3(64), 0, st,
+                       p->d_windows, p->sb[par].out);
+}
+
+// sync path (run / run_partial), after msm_sync_t has drained the pipeline:
+// the stages at parity 0 on the null stream, the phase events between them
+template <typename C, typename CFG>
+static int msm_run_sync_cfg(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
+    constexpr int JB = msm_plan_t<C>::JB;
     HIP_TRY(hipEventRecord(p->ev[0], 0));
-    hipError_t e = fbm_enqueue_sort_chain<C, CFG>(p, 0, 0);
-    if (e != hipSuccess) return hip_fail(e, "merged fixed-base sort chain");
+    hipError_t e = msm_enqueue_sort_chain<C, CFG>(p, 0, 0);
+    if (e != hipSuccess) return hip_fail(e, "sort chain");
     HIP_TRY(hipEventRecord(p->ev[1], 0));
-    fbm_enqueue_walk<C, CFG>(p, 0, 0);
+    bool tree_done = false;
+    if constexpr (std::is_same_v<C, Bn254G1> && std::is_same_v<CFG, CfgL254>) {
+        if (p->use_tree) {
+            e = msm_enqueue_tree_walk<C, CFG>(p, 0, 0);
+            tree_done = true;
+        }
+    }
+    if (!tree_done) e = msm_enqueue_walk<C, CFG>(p, 0, 0);
+    if (e != hipSuccess) return hip_fail(e, "bucket walk");
     HIP_TRY(hipEventRecord(p->ev[2], 0));
-    fbm_enqueue_reduce<C, CFG>(p, 0, 0);
+    msm_enqueue_reduce<C, CFG>(p, 0, 0);
     HIP_TRY(hipEventRecord(p->ev[3], 0));
+    msm_enqueue_emit<C, CFG>(p, 0, 0);
     HIP_TRY(hipEventRecord(p->ev[4], 0));
-    uint8_t wire[msm_plan_t<C>::JB];
-    HIP_TRY(hipMemcpy(wire, p->d_out, msm_plan_t<C>::JB,
-                      hipMemcpyDeviceToHost));
-    host_windows_horner<C>(wire, 1, CFG::C, out, out_mode);
+    uint8_t wire[CFG::NWIN * JB];
+    HIP_TRY(hipMemcpy(wire, p->sb[0].out, sizeof wire, hipMemcpyDeviceToHost));
+    host_windows_horner<C>(wire, CFG::NWIN, CFG::C, out, out_mode);
     HIP_TRY(hipDeviceSynchronize());
+    // digits+sort, walk, reduce, emit, total
     const int a[5] = {0, 1, 2, 3, 0}, b[5] = {1, 2, 3, 4, 4};
     for (int i = 0; i < 5; i++) {
         float ms;
@@ -977,132 +995,6 @@ static int msm_run_fbm(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
         p->last_ms[i] = ms;
     }
     return EM_OK;
-}
-
-template <typename C, typename CFG>
-static hipError_t msm_enqueue_sort_chain(msm_plan_t<C> *p, int par,
-                                         hipStream_t ss) {
-    if constexpr (is_fbm<CFG>::value) {
-        return fbm_enqueue_sort_chain<C, CFG>(p, par, ss);
-    } else {
-    constexpr bool FB = std::is_same_v<CFG, CfgFB>;
-    size_t total = FB ? p->n * (size_t)FB_NWIN : p->n * (size_t)CFG::NWIN;
-    uint32_t *KO = par ? p->d_keys_out2 : p->d_keys_out;
-    uint32_t *VO = par ? p->d_vals_out2 : p->d_vals_out;
-    uint32_t *OFF = par ? p->d_offsets2 : p->d_offsets;
-    uint32_t *SCH = par ? p->d_sched2 : p->d_sched;
-    if constexpr (FB) {
-        hipLaunchKernelGGL(k_fb_digits, dim3(blocks_for(total, 256)),
-                           dim3(256), 0, ss, p->d_scalars, p->d_inf,
-                           p->d_keys, p->d_vals, p->n);
-    } else if (p->keys16) {
-        hipLaunchKernelGGL((k_digits<CFG, uint16_t>),
-                           dim3(blocks_for(p->n, 256)), dim3(256), 0, ss,
-                           p->d_scalars, p->d_inf, (uint16_t *)p->d_keys,
-                           p->d_vals, p->n);
-    } else {
-        hipLaunchKernelGGL((k_digits<CFG>), dim3(blocks_for(p->n, 256)),
-                           dim3(256), 0, ss, p->d_scalars, p->d_inf,
-                           p->d_keys, p->d_vals, p->n);
-    }
-    if (!FB && p->keys16) {
-        for (int w = 0; w < CFG::NWIN; w++) {
-            size_t tmp = p->sort_tmp_bytes;
-            size_t off = (size_t)w * p->n;
-            EM_HT(rocprim::radix_sort_pairs(
-                p->d_sort_tmp, tmp, (const uint16_t *)p->d_keys + off,
-                (uint16_t *)KO + off, p->d_vals + off, VO + off, p->n, 0,
-                CFG::DBITS, ss));
-        }
-    } else {
-        size_t tmp = p->sort_tmp_bytes;
-        EM_HT(rocprim::radix_sort_pairs(p->d_sort_tmp, tmp, p->d_keys, KO,
-                                        p->d_vals, VO, total, 0,
-                                        CFG::SORT_BITS, ss));
-    }
-    if (!FB && p->keys16) {
-        hipLaunchKernelGGL((k_offsets_seg<CFG>),
-                           dim3(blocks_for((size_t)CFG::NBUCKETS + 1, 256)),
-                           dim3(256), 0, ss, (const uint16_t *)KO, p->n, OFF);
-    } else {
-        hipLaunchKernelGGL((k_offsets<CFG>),
-                           dim3(blocks_for((size_t)CFG::NBUCKETS + 1, 256)),
-                           dim3(256), 0, ss, KO, total, OFF);
-    }
-    hipLaunchKernelGGL((k_bucket_lengths<CFG>),
-                       dim3(blocks_for(CFG::NBUCKETS, 256)), dim3(256), 0, ss,
-                       OFF, p->d_blen, p->d_bids);
-    size_t tmp2 = p->sort_tmp_bytes;
-    EM_HT(rocprim::radix_sort_pairs(p->d_sort_tmp, tmp2, p->d_blen,
-                                    p->d_blen_out, p->d_bids, SCH,
-                                    (size_t)CFG::NBUCKETS, 0, 32, ss));
-    return hipSuccess;
-    }
-}
-
-// compute chain: bucket walk -> reduction -> window emission.  in_graph
-// runs the plain single-launch walk (event records stay OUTSIDE graphs);
-// the direct path keeps the EM_MSM_SPLIT gate experiment.
-template <typename C, typename CFG>
-static hipError_t msm_enqueue_comp_chain(msm_plan_t<C> *p, int par,
-                                         const g1aT<C> *pts, hipStream_t sc,
-                                         bool in_graph) {
-    if constexpr (is_fbm<CFG>::value) {
-        if (!in_graph) EM_HT(hipEventRecord(p->ev_walkA[par], sc));
-        fbm_enqueue_walk<C, CFG>(p, par, sc);
-        fbm_enqueue_reduce<C, CFG>(p, par, sc);
-        return hipSuccess;
-    } else {
-    uint32_t *VO = par ? p->d_vals_out2 : p->d_vals_out;
-    uint32_t *OFF = par ? p->d_offsets2 : p->d_offsets;
-    uint32_t *SCH = par ? p->d_sched2 : p->d_sched;
-    uint8_t *DOUT = par ? p->d_out2 : p->d_out;
-    static int spct = std::getenv("EM_MSM_SPLIT")
-                          ? atoi(std::getenv("EM_MSM_SPLIT"))
-                          : 0;
-    if (in_graph || spct <= 0) {
-        // gate off (A/B-measured default: gating the sorts on part of the
-        // walk only LOST time — the async gap is host pacing, which the
-        // graph path removes instead)
-        if (!in_graph)
-            EM_HT(hipEventRecord(p->ev_walkA[par], sc));
-        hipLaunchKernelGGL((k_bucket_acc<C, CFG>),
-                           dim3(blocks_for(CFG::NBUCKETS, 256)), dim3(256),
-                           0, sc, pts, VO, OFF, SCH, p->d_buckets, 0u);
-    } else {
-        uint32_t splitA =
-            (uint32_t)(((uint64_t)CFG::NBUCKETS * (uint32_t)spct) / 100);
-        splitA = (splitA / 256) * 256;
-        if (splitA == 0 || splitA >= CFG::NBUCKETS) {
-            hipLaunchKernelGGL((k_bucket_acc<C, CFG>),
-                               dim3(blocks_for(CFG::NBUCKETS, 256)),
-                               dim3(256), 0, sc, pts, VO, OFF, SCH,
-                               p->d_buckets, 0u);
-            EM_HT(hipEventRecord(p->ev_walkA[par], sc));
-        } else {
-            hipLaunchKernelGGL((k_bucket_acc<C, CFG>),
-                               dim3(blocks_for(splitA, 256)), dim3(256), 0,
-                               sc, pts, VO, OFF, SCH, p->d_buckets, 0u);
-            EM_HT(hipEventRecord(p->ev_walkA[par], sc));
-            hipLaunchKernelGGL((k_bucket_acc<C, CFG>),
-                               dim3(blocks_for(CFG::NBUCKETS - splitA, 256)),
-                               dim3(256), 0, sc, pts, VO, OFF, SCH,
-                               p->d_buckets, splitA);
-        }
-    }
-    hipLaunchKernelGGL((k_segment_reduce<C, CFG>),
-                       dim3(blocks_for(CFG::NWIN * CFG::NSEG, 256)), dim3(256),
-                       0, sc, p->d_buckets, p->d_seg_sum, p->d_seg_wsum);
-    hipLaunchKernelGGL((k_weighted_reduce<C, CFG>),
-                       dim3(blocks_for(CFG::NWIN * CFG::NSEG, CFG::RED_BLOCK)),
-                       dim3(CFG::RED_BLOCK), 0, sc, p->d_seg_sum,
-                       p->d_seg_wsum, p->d_partials);
-    hipLaunchKernelGGL((k_window_sum<C, CFG>), dim3(CFG::NWIN), dim3(64), 0,
-                       sc, p->d_partials, p->d_windows);
-    hipLaunchKernelGGL((k_emit_windows<C, CFG>), dim3(1), dim3(64), 0, sc,
-                       p->d_windows, DOUT);
-    return hipSuccess;
-    }
 }
 
 // capture one chain as a hipGraph on `st` and instantiate it
@@ -1124,23 +1016,22 @@ static int msm_capture_graph(hipStream_t st, hipGraphExec_t *exec, F enqueue,
 }
 
 // one pipelined step: sort chain on s_sort (buffers chosen by step parity),
-// compute chain on s_comp ordered behind it by event.  Returns after
-// ENQUEUE; the result lands in `out` by the time msm_sync (or the depth-2
-// backpressure of a later run_async) returns.  The proving loop runs many
-// MSMs back-to-back, so steady-state cost = max(sort chain, compute chain)
-// instead of their sum.
+// compute chain (walk, reduce, emit) on s_comp ordered behind it by event.
+// Returns after ENQUEUE; the result lands in `out` by the time msm_sync (or
+// the depth-2 backpressure of a later run_async) returns.  The proving loop
+// runs many MSMs back-to-back, so steady-state cost = max(sort chain,
+// compute chain) instead of their sum.
 //
 // A step is ~70 dispatches (15 per-window rocPRIM sorts alone), so by
 // default both chains are CAPTURED per parity as hipGraphs and replayed
 // as two graph launches — the measured async-over-compute-chain gap was
 // host dispatch pacing.  All pointers are parity-fixed; graphs rebuild if
 // the point table changes (fixed-base precompute).  EM_MSM_GRAPH=0
-// disables; the EM_MSM_SPLIT gate experiment implies the direct path.
+// disables; the EM_MSM_SPLIT gate experiment implies the direct path, and
+// so does the tree experiment (which then runs the plain XYZZ walk here).
 template <typename C, typename CFG>
 static int msm_run_async_cfg(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
-    // both fixed-base modes gather from the table and emit one window
-    constexpr bool FB = std::is_same_v<CFG, CfgFB> || is_fbm<CFG>::value;
-    const g1aT<C> *pts = FB ? p->d_pts_ext : p->d_pts;
+    const g1aT<C> *pts = msm_walk_pts<C, CFG>(p);
     int par = p->apar;
     int rc = msm_deliver(p, par);  // free this parity's slots (step k-2)
     if (rc) return rc;
@@ -1148,10 +1039,20 @@ static int msm_run_async_cfg(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
     static bool graph_on = std::getenv("EM_MSM_GRAPH")
                                ? atoi(std::getenv("EM_MSM_GRAPH")) != 0
                                : true;
-    static bool split_on = std::getenv("EM_MSM_SPLIT")
-                               ? atoi(std::getenv("EM_MSM_SPLIT")) > 0
-                               : false;
+    const bool split_on = msm_split_pct() > 0;
     bool use_graph = graph_on && !split_on && !p->use_tree;
+    // ev_walkA[par] gates the NEXT step's sort chain.  Gate off (A/B-measured
+    // default: gating the sorts on part of the walk only LOST time — the
+    // async gap is host pacing, which the graph path removes instead): it is
+    // recorded before the walk.  EM_MSM_SPLIT: the window walk records it.
+    hipEvent_t mid =
+        split_on && !is_fbm<CFG>::value ? p->ev_walkA[par] : nullptr;
+    auto comp_chain = [&](hipEvent_t m) -> hipError_t {
+        EM_HT((msm_enqueue_walk<C, CFG>(p, par, sc, m)));
+        msm_enqueue_reduce<C, CFG>(p, par, sc);
+        msm_enqueue_emit<C, CFG>(p, par, sc);
+        return hipSuccess;
+    };
     HIP_TRY(hipStreamWaitEvent(ss, p->ev_comp_done[par], 0));
     // contention gate: wait for the PREVIOUS step's walk segment A
     HIP_TRY(hipStreamWaitEvent(ss, p->ev_walkA[par ^ 1], 0));
@@ -1171,10 +1072,7 @@ static int msm_run_async_cfg(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
             "sort-chain graph capture");
         if (rc) return rc;
         rc = msm_capture_graph(
-            sc, &p->gx_comp[par],
-            [&]() {
-                return msm_enqueue_comp_chain<C, CFG>(p, par, pts, sc, true);
-            },
+            sc, &p->gx_comp[par], [&]() { return comp_chain(nullptr); },
             "compute-chain graph capture");
         if (rc) return rc;
         p->gx_pts[par] = (const void *)pts;
@@ -1189,20 +1087,18 @@ static int msm_run_async_cfg(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
     HIP_TRY(hipEventRecord(p->ev_sort_done[par], ss));
     // ---- compute chain ----
     HIP_TRY(hipStreamWaitEvent(sc, p->ev_sort_done[par], 0));
+    if (!mid) HIP_TRY(hipEventRecord(p->ev_walkA[par], sc));
     if (use_graph) {
-        HIP_TRY(hipEventRecord(p->ev_walkA[par], sc));  // gate-off marker
         HIP_TRY(hipGraphLaunch(p->gx_comp[par], sc));
     } else {
-        hipError_t ec = msm_enqueue_comp_chain<C, CFG>(p, par, pts, sc, false);
+        hipError_t ec = comp_chain(mid);
         if (ec != hipSuccess) return hip_fail(ec, "compute chain (async)");
     }
-    uint8_t *DOUT = par ? p->d_out2 : p->d_out;
-    constexpr int NW = FB ? 1 : CFG::NWIN;
-    HIP_TRY(hipMemcpyAsync(p->h_out[par], DOUT,
-                           (size_t)NW * msm_plan_t<C>::JB,
+    HIP_TRY(hipMemcpyAsync(p->h_out[par], p->sb[par].out,
+                           (size_t)CFG::NWIN * msm_plan_t<C>::JB,
                            hipMemcpyDeviceToHost, sc));
     HIP_TRY(hipEventRecord(p->ev_comp_done[par], sc));
-    p->pend[par] = {out, out_mode, NW, CFG::C, true};
+    p->pend[par] = {out, out_mode, CFG::NWIN, CFG::C, true};
     p->apar ^= 1;
     return EM_OK;
 }
@@ -1214,27 +1110,9 @@ static int msm_run_async_t(msm_plan_t<C> *p, uint8_t *out, int out_mode = 0) {
         g_last_err = "msm_run_async: points/scalars not uploaded";
         return EM_ERR_INPUT;
     }
-    if constexpr (msm_curve<C>::FB_MERGED) {
-        if (p->fb_c)
-            return fbm_dispatch(p->fb_c, [&](auto cfg) {
-                return msm_run_async_cfg<C, decltype(cfg)>(p, out, out_mode);
-            });
-    }
-    if constexpr (!msm_curve<C>::SIGNED_ONLY) {
-        if (p->fixed_base) return msm_run_async_cfg<C, CfgFB>(p, out, out_mode);
-    }
-    if (p->cbits == 8)
-        return msm_run_async_cfg<C, msm_cfg<8, msm_plan_t<C>::SB>>(p, out,
-                                                                   out_mode);
-    if constexpr (msm_curve<C>::BN_SCALARS) {
-        if (p->cbits == 17)
-            return msm_run_async_cfg<C, CfgSg254>(p, out, out_mode);
-    }
-    if constexpr (msm_curve<C>::SIGNED_ONLY)
-        return EM_ERR_INPUT;  // unreachable: create picks 8 or 17
-    else
-        return msm_run_async_cfg<C, msm_cfg<16, msm_plan_t<C>::SB>>(p, out,
-                                                                    out_mode);
+    return msm_with_cfg(p, [&](auto cfg) {
+        return msm_run_async_cfg<C, decltype(cfg)>(p, out, out_mode);
+    });
 }
 
 template <typename C>
@@ -1246,24 +1124,9 @@ static int msm_run_inner_t(msm_plan_t<C> *p, uint8_t *out, int out_mode) {
     }
     int rc = msm_sync_t(p);  // drain any pipelined steps first
     if (rc) return rc;
-    if constexpr (msm_curve<C>::FB_MERGED) {
-        if (p->fb_c)
-            return fbm_dispatch(p->fb_c, [&](auto cfg) {
-                return msm_run_fbm<C, decltype(cfg)>(p, out, out_mode);
-            });
-    }
-    if constexpr (!msm_curve<C>::SIGNED_ONLY) {
-        if (p->fixed_base) return msm_run_cfg<C, CfgFB>(p, out, out_mode);
-    }
-    if (p->cbits == 8)
-        return msm_run_cfg<C, msm_cfg<8, msm_plan_t<C>::SB>>(p, out, out_mode);
-    if constexpr (msm_curve<C>::BN_SCALARS) {
-        if (p->cbits == 17) return msm_run_cfg<C, CfgSg254>(p, out, out_mode);
-    }
-    if constexpr (msm_curve<C>::SIGNED_ONLY)
-        return EM_ERR_INPUT;  // unreachable: create picks 8 or 17
-    else
-        return msm_run_cfg<C, msm_cfg<16, msm_plan_t<C>::SB>>(p, out, out_mode);
+    return msm_with_cfg(p, [&](auto cfg) {
+        return msm_run_sync_cfg<C, decltype(cfg)>(p, out, out_mode);
+    });
 }
 
 // opaque ABI types

@@ -136,59 +136,118 @@ def gen_fr(seed: int, n: int) -> bytes:
     return bytes(out)
 
 
-class MsmPlan:
-    """Device-resident MSM plan: upload once, run many (bench/pipeline)."""
+class _MsmPlanBase:
+    """What the four device-resident MSM plans share.  A subclass names its
+    ABI family (functions ethrex_mi355_<_PREFIX>_<op>, error labels
+    <_PREFIX>_<op>), its affine and Jacobian point sizes, and in _OPS every
+    op it may call."""
+
+    _PREFIX = None
+    _AFF = 0   # bytes of an affine point (points, run, run_async)
+    _JAC = 0   # bytes of a Jacobian partial (run_partial)
+    _OPS = ("plan_create", "plan_destroy", "upload_points", "gen_points",
+            "download_points", "upload_scalars", "run", "run_partial",
+            "run_async", "sync", "last_times")
+
+    @classmethod
+    def _fn(cls, op):
+        if op not in cls._OPS:
+            raise AttributeError(f"{cls.__name__}: undeclared op {op}")
+        return getattr(_lib, f"ethrex_mi355_{cls._PREFIX}_{op}")
+
+    def _call(self, op, *args):
+        _check(self._fn(op)(self._p, *args), f"{self._PREFIX}_{op}")
+
+    def _call_out(self, op, nbytes):
+        out = (ctypes.c_uint8 * nbytes)()
+        self._call(op, out)
+        return out
 
     def __init__(self, n: int):
         self.n = n
         self._p = ctypes.c_void_p()
         self._pending = []
-        _check(_lib.ethrex_mi355_msm_plan_create(ctypes.c_size_t(n),
-                                                 ctypes.byref(self._p)),
-               "msm_plan_create")
+        _check(self._fn("plan_create")(ctypes.c_size_t(n),
+                                       ctypes.byref(self._p)),
+               f"{self._PREFIX}_plan_create")
 
     def upload_points(self, points: bytes):
-        _check(_lib.ethrex_mi355_msm_upload_points(self._p, _buf(points)),
-               "msm_upload_points")
+        self._call("upload_points", _buf(points))
 
     def gen_points(self, start: int = 0):
-        _check(_lib.ethrex_mi355_msm_gen_points(self._p, ctypes.c_uint64(start)),
-               "msm_gen_points")
+        self._call("gen_points", ctypes.c_uint64(start))
 
     def download_points(self) -> bytes:
-        out = (ctypes.c_uint8 * (64 * self.n))()
-        _check(_lib.ethrex_mi355_msm_download_points(self._p, out),
-               "msm_download_points")
-        return bytes(out)
+        return bytes(self._call_out("download_points", self._AFF * self.n))
 
     def upload_scalars(self, scalars: bytes):
-        _check(_lib.ethrex_mi355_msm_upload_scalars(self._p, _buf(scalars)),
-               "msm_upload_scalars")
+        self._call("upload_scalars", _buf(scalars))
+
+    def _scalars_from_ntt(self, src, offset):
+        # any source with a device_data() -> (ptr, n) accessor: an NttPlan
+        # or a QuotPlan (whose h feeds the Z-basis MSM)
+        ptr, nn = src.device_data()
+        if offset + self.n > nn:
+            raise HipCoreError(EM_ERR_INPUT,
+                               f"scalars_from_ntt: offset {offset} + n "
+                               f"{self.n} exceeds NTT size {nn}")
+        self._call("scalars_from_ntt", ptr, ctypes.c_uint64(offset))
 
     def run(self) -> bytes:
-        out = (ctypes.c_uint8 * 64)()
-        _check(_lib.ethrex_mi355_msm_run(self._p, out), "msm_run")
-        return bytes(out)
+        return bytes(self._call_out("run", self._AFF))
 
     def run_partial(self) -> bytes:
-        out = (ctypes.c_uint8 * 96)()
-        _check(_lib.ethrex_mi355_msm_run_partial(self._p, out), "msm_run_partial")
-        return bytes(out)
+        return bytes(self._call_out("run_partial", self._JAC))
+
+    def run_async(self):
+        """Enqueue one pipelined MSM step (sort chain of the next step
+        overlaps this step's compute chain).  Result delivered at sync()."""
+        self._pending.append(self._call_out("run_async", self._AFF))
+
+    def sync(self) -> bytes:
+        """Drain the pipeline; returns the LAST pipelined result."""
+        self._call("sync")
+        outs = [bytes(b) for b in self._pending]
+        self._pending = []
+        return outs[-1] if outs else b""
 
     def last_times(self):
         t = (ctypes.c_double * 5)()
-        _check(_lib.ethrex_mi355_msm_last_times(self._p, t), "msm_last_times")
+        self._call("last_times", t)
         return {"digits_sort_ms": t[0], "bucket_acc_ms": t[1],
-                "reduce_ms": t[2], "combine_ms": t[3], "total_ms": t[4],
-                "fb_precompute_ms": self._fb_info()[1]}
+                "reduce_ms": t[2], "combine_ms": t[3], "total_ms": t[4]}
+
+    def destroy(self):
+        if self._p:
+            self._fn("plan_destroy")(self._p)
+            self._p = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class MsmPlan(_MsmPlanBase):
+    """Device-resident MSM plan: upload once, run many (bench/pipeline)."""
+
+    _PREFIX, _AFF, _JAC = "msm", 64, 96
+    _OPS = _MsmPlanBase._OPS + (
+        "fb_info", "download_fb_rows", "run_partial_async", "wait_one",
+        "scalars_from_ntt", "combine")
+
+    def last_times(self):
+        t = super().last_times()
+        t["fb_precompute_ms"] = self._fb_info()[1]
+        return t
 
     def _fb_info(self):
         c = ctypes.c_int(0)
         ms = ctypes.c_double(0.0)
         nbytes = ctypes.c_uint64(0)
-        _check(_lib.ethrex_mi355_msm_fb_info(
-            self._p, ctypes.byref(c), ctypes.byref(ms), ctypes.byref(nbytes)),
-            "msm_fb_info")
+        self._call("fb_info", ctypes.byref(c), ctypes.byref(ms),
+                   ctypes.byref(nbytes))
         return c.value, ms.value, nbytes.value
 
     @property
@@ -206,32 +265,14 @@ class MsmPlan:
         """Rows [start, start+count) of window w of the fixed-base table
         as 64-byte affine points (parity tests)."""
         out = (ctypes.c_uint8 * (64 * count))()
-        _check(_lib.ethrex_mi355_msm_download_fb_rows(
-            self._p, ctypes.c_int(w), ctypes.c_size_t(start),
-            ctypes.c_size_t(count), out), "msm_download_fb_rows")
+        self._call("download_fb_rows", ctypes.c_int(w),
+                   ctypes.c_size_t(start), ctypes.c_size_t(count), out)
         return bytes(out)
-
-    def run_async(self):
-        """Enqueue one pipelined MSM step (sort chain of the next step
-        overlaps this step's compute chain).  Result delivered at sync()."""
-        buf = (ctypes.c_uint8 * 64)()
-        _check(_lib.ethrex_mi355_msm_run_async(self._p, buf), "msm_run_async")
-        self._pending.append(buf)
 
     def run_partial_async(self):
         """Pipelined shard step: delivers the 96-B Jacobian partial at
         sync() (the N>1 exchange payload)."""
-        buf = (ctypes.c_uint8 * 96)()
-        _check(_lib.ethrex_mi355_msm_run_partial_async(self._p, buf),
-               "msm_run_partial_async")
-        self._pending.append(buf)
-
-    def sync(self) -> bytes:
-        """Drain the pipeline; returns the LAST pipelined result."""
-        _check(_lib.ethrex_mi355_msm_sync(self._p), "msm_sync")
-        outs = [bytes(b) for b in self._pending]
-        self._pending = []
-        return outs[-1] if outs else b""
+        self._pending.append(self._call_out("run_partial_async", self._JAC))
 
     def wait_one(self) -> bytes:
         """Deliver ONLY the oldest pending pipelined step (later steps keep
@@ -239,7 +280,7 @@ class MsmPlan:
         the GPU computes step k+1."""
         if not self._pending:
             return b""
-        _check(_lib.ethrex_mi355_msm_wait_one(self._p), "msm_wait_one")
+        self._call("wait_one")
         return bytes(self._pending.pop(0))
 
     def scalars_from_ntt(self, ntt_plan, offset: int = 0):
@@ -247,34 +288,13 @@ class MsmPlan:
         plan's device-resident output at element `offset` (on-device, no
         PCIe; the sp1.rs:122-134 wrap flow feeds the witness NTT output
         into the proving MSM)."""
-        # any source with a device_data() -> (ptr, n) accessor: an NttPlan
-        # or a QuotPlan (whose h feeds the Z-basis MSM)
-        ptr, nn = ntt_plan.device_data()
-        if offset + self.n > nn:
-            raise HipCoreError(EM_ERR_INPUT,
-                               f"scalars_from_ntt: offset {offset} + n "
-                               f"{self.n} exceeds NTT size {nn}")
-        _check(_lib.ethrex_mi355_msm_scalars_from_ntt(
-            self._p, ptr, ctypes.c_uint64(offset)), "msm_scalars_from_ntt")
+        self._scalars_from_ntt(ntt_plan, offset)
 
     def combine(self, jacobians: bytes, count: int) -> bytes:
         """combine Jacobian partials reusing this plan's device buffers"""
         out = (ctypes.c_uint8 * 64)()
-        _check(_lib.ethrex_mi355_msm_combine(self._p, _buf(jacobians),
-                                             ctypes.c_size_t(count), out),
-               "msm_combine")
+        self._call("combine", _buf(jacobians), ctypes.c_size_t(count), out)
         return bytes(out)
-
-    def destroy(self):
-        if self._p:
-            _lib.ethrex_mi355_msm_plan_destroy(self._p)
-            self._p = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 class NttPlan:
@@ -473,81 +493,15 @@ def bls_gen_fr(seed: int, n: int) -> bytes:
     return bytes(out)
 
 
-class BlsMsmPlan:
+class BlsMsmPlan(_MsmPlanBase):
     """Device-resident BLS12-381 G1 MSM plan (blob-KZG commitment shape)."""
 
-    def __init__(self, n: int):
-        self.n = n
-        self._p = ctypes.c_void_p()
-        self._pending = []
-        _check(_lib.ethrex_mi355_bls_msm_plan_create(ctypes.c_size_t(n),
-                                                     ctypes.byref(self._p)),
-               "bls_msm_plan_create")
-
-    def upload_points(self, points: bytes):
-        _check(_lib.ethrex_mi355_bls_msm_upload_points(self._p, _buf(points)),
-               "bls_msm_upload_points")
-
-    def gen_points(self, start: int = 0):
-        _check(_lib.ethrex_mi355_bls_msm_gen_points(self._p,
-                                                    ctypes.c_uint64(start)),
-               "bls_msm_gen_points")
-
-    def download_points(self) -> bytes:
-        out = (ctypes.c_uint8 * (96 * self.n))()
-        _check(_lib.ethrex_mi355_bls_msm_download_points(self._p, out),
-               "bls_msm_download_points")
-        return bytes(out)
-
-    def upload_scalars(self, scalars: bytes):
-        _check(_lib.ethrex_mi355_bls_msm_upload_scalars(self._p, _buf(scalars)),
-               "bls_msm_upload_scalars")
+    _PREFIX, _AFF, _JAC = "bls_msm", 96, 144
+    _OPS = _MsmPlanBase._OPS + ("precompute",)
 
     def precompute(self):
         """fixed-base table (setup points fixed across blobs)"""
-        _check(_lib.ethrex_mi355_bls_msm_precompute(self._p),
-               "bls_msm_precompute")
-
-    def run(self) -> bytes:
-        out = (ctypes.c_uint8 * 96)()
-        _check(_lib.ethrex_mi355_bls_msm_run(self._p, out), "bls_msm_run")
-        return bytes(out)
-
-    def run_partial(self) -> bytes:
-        out = (ctypes.c_uint8 * 144)()
-        _check(_lib.ethrex_mi355_bls_msm_run_partial(self._p, out),
-               "bls_msm_run_partial")
-        return bytes(out)
-
-    def run_async(self):
-        buf = (ctypes.c_uint8 * 96)()
-        _check(_lib.ethrex_mi355_bls_msm_run_async(self._p, buf),
-               "bls_msm_run_async")
-        self._pending.append(buf)
-
-    def sync(self) -> bytes:
-        _check(_lib.ethrex_mi355_bls_msm_sync(self._p), "bls_msm_sync")
-        outs = [bytes(b) for b in self._pending]
-        self._pending = []
-        return outs[-1] if outs else b""
-
-    def last_times(self):
-        t = (ctypes.c_double * 5)()
-        _check(_lib.ethrex_mi355_bls_msm_last_times(self._p, t),
-               "bls_msm_last_times")
-        return {"digits_sort_ms": t[0], "bucket_acc_ms": t[1],
-                "reduce_ms": t[2], "combine_ms": t[3], "total_ms": t[4]}
-
-    def destroy(self):
-        if self._p:
-            _lib.ethrex_mi355_bls_msm_plan_destroy(self._p)
-            self._p = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        self._call("precompute")
 
 
 def bls_g2_add(p1: bytes, p2: bytes):
@@ -569,78 +523,10 @@ def bls_g2_msm(points: bytes, scalars: bytes, n: int):
     return rc, bytes(out)
 
 
-class BlsG2MsmPlan:
+class BlsG2MsmPlan(_MsmPlanBase):
     """Device-resident BLS12-381 G2 MSM plan (EIP-2537 G2MSM shape)."""
 
-    def __init__(self, n: int):
-        self.n = n
-        self._p = ctypes.c_void_p()
-        self._pending = []
-        _check(_lib.ethrex_mi355_bls_g2_msm_plan_create(ctypes.c_size_t(n),
-                                                        ctypes.byref(self._p)),
-               "bls_g2_msm_plan_create")
-
-    def upload_points(self, points: bytes):
-        _check(_lib.ethrex_mi355_bls_g2_msm_upload_points(self._p,
-                                                          _buf(points)),
-               "bls_g2_msm_upload_points")
-
-    def gen_points(self, start: int = 0):
-        _check(_lib.ethrex_mi355_bls_g2_msm_gen_points(
-            self._p, ctypes.c_uint64(start)), "bls_g2_msm_gen_points")
-
-    def download_points(self) -> bytes:
-        out = (ctypes.c_uint8 * (192 * self.n))()
-        _check(_lib.ethrex_mi355_bls_g2_msm_download_points(self._p, out),
-               "bls_g2_msm_download_points")
-        return bytes(out)
-
-    def upload_scalars(self, scalars: bytes):
-        _check(_lib.ethrex_mi355_bls_g2_msm_upload_scalars(self._p,
-                                                           _buf(scalars)),
-               "bls_g2_msm_upload_scalars")
-
-    def run(self) -> bytes:
-        out = (ctypes.c_uint8 * 192)()
-        _check(_lib.ethrex_mi355_bls_g2_msm_run(self._p, out),
-               "bls_g2_msm_run")
-        return bytes(out)
-
-    def run_partial(self) -> bytes:
-        out = (ctypes.c_uint8 * 288)()
-        _check(_lib.ethrex_mi355_bls_g2_msm_run_partial(self._p, out),
-               "bls_g2_msm_run_partial")
-        return bytes(out)
-
-    def run_async(self):
-        buf = (ctypes.c_uint8 * 192)()
-        _check(_lib.ethrex_mi355_bls_g2_msm_run_async(self._p, buf),
-               "bls_g2_msm_run_async")
-        self._pending.append(buf)
-
-    def sync(self) -> bytes:
-        _check(_lib.ethrex_mi355_bls_g2_msm_sync(self._p), "bls_g2_msm_sync")
-        outs = [bytes(b) for b in self._pending]
-        self._pending = []
-        return outs[-1] if outs else b""
-
-    def last_times(self):
-        t = (ctypes.c_double * 5)()
-        _check(_lib.ethrex_mi355_bls_g2_msm_last_times(self._p, t),
-               "bls_g2_msm_last_times")
-        return {"digits_sort_ms": t[0], "bucket_acc_ms": t[1],
-                "reduce_ms": t[2], "combine_ms": t[3], "total_ms": t[4]}
-
-    def destroy(self):
-        if self._p:
-            _lib.ethrex_mi355_bls_g2_msm_plan_destroy(self._p)
-            self._p = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+    _PREFIX, _AFF, _JAC = "bls_g2_msm", 192, 288
 
 
 # ==== BN254 G2 (the Groth16 B-query; EIP-197 byte semantics) ====
@@ -677,92 +563,17 @@ def bn254_g2_msm(points: bytes, scalars: bytes, n: int):
     return rc, bytes(out)
 
 
-class Bn254G2MsmPlan:
+class Bn254G2MsmPlan(_MsmPlanBase):
     """Device-resident BN254 G2 MSM plan (Groth16 B2 = sum w_i * B_i)."""
 
-    def __init__(self, n: int):
-        self.n = n
-        self._p = ctypes.c_void_p()
-        self._pending = []
-        _check(_lib.ethrex_mi355_bn254_g2_msm_plan_create(
-            ctypes.c_size_t(n), ctypes.byref(self._p)),
-            "bn254_g2_msm_plan_create")
-
-    def upload_points(self, points: bytes):
-        _check(_lib.ethrex_mi355_bn254_g2_msm_upload_points(self._p,
-                                                            _buf(points)),
-               "bn254_g2_msm_upload_points")
-
-    def gen_points(self, start: int = 0):
-        _check(_lib.ethrex_mi355_bn254_g2_msm_gen_points(
-            self._p, ctypes.c_uint64(start)), "bn254_g2_msm_gen_points")
-
-    def download_points(self) -> bytes:
-        out = (ctypes.c_uint8 * (128 * self.n))()
-        _check(_lib.ethrex_mi355_bn254_g2_msm_download_points(self._p, out),
-               "bn254_g2_msm_download_points")
-        return bytes(out)
-
-    def upload_scalars(self, scalars: bytes):
-        _check(_lib.ethrex_mi355_bn254_g2_msm_upload_scalars(self._p,
-                                                             _buf(scalars)),
-               "bn254_g2_msm_upload_scalars")
+    _PREFIX, _AFF, _JAC = "bn254_g2_msm", 128, 192
+    _OPS = _MsmPlanBase._OPS + ("scalars_from_ntt",)
 
     def scalars_from_ntt(self, ntt_plan, offset: int = 0):
         """take this plan's n scalars from an NttPlan / QuotPlan's
         device-resident vector at element `offset` (on device, no PCIe):
         the witness vector feeds B2 directly"""
-        ptr, nn = ntt_plan.device_data()
-        if offset + self.n > nn:
-            raise HipCoreError(EM_ERR_INPUT,
-                               f"scalars_from_ntt: offset {offset} + n "
-                               f"{self.n} exceeds NTT size {nn}")
-        _check(_lib.ethrex_mi355_bn254_g2_msm_scalars_from_ntt(
-            self._p, ptr, ctypes.c_uint64(offset)),
-            "bn254_g2_msm_scalars_from_ntt")
-
-    def run(self) -> bytes:
-        out = (ctypes.c_uint8 * 128)()
-        _check(_lib.ethrex_mi355_bn254_g2_msm_run(self._p, out),
-               "bn254_g2_msm_run")
-        return bytes(out)
-
-    def run_partial(self) -> bytes:
-        out = (ctypes.c_uint8 * 192)()
-        _check(_lib.ethrex_mi355_bn254_g2_msm_run_partial(self._p, out),
-               "bn254_g2_msm_run_partial")
-        return bytes(out)
-
-    def run_async(self):
-        buf = (ctypes.c_uint8 * 128)()
-        _check(_lib.ethrex_mi355_bn254_g2_msm_run_async(self._p, buf),
-               "bn254_g2_msm_run_async")
-        self._pending.append(buf)
-
-    def sync(self) -> bytes:
-        _check(_lib.ethrex_mi355_bn254_g2_msm_sync(self._p),
-               "bn254_g2_msm_sync")
-        outs = [bytes(b) for b in self._pending]
-        self._pending = []
-        return outs[-1] if outs else b""
-
-    def last_times(self):
-        t = (ctypes.c_double * 5)()
-        _check(_lib.ethrex_mi355_bn254_g2_msm_last_times(self._p, t),
-               "bn254_g2_msm_last_times")
-        return {"digits_sort_ms": t[0], "bucket_acc_ms": t[1],
-                "reduce_ms": t[2], "combine_ms": t[3], "total_ms": t[4]}
-
-    def destroy(self):
-        if self._p:
-            _lib.ethrex_mi355_bn254_g2_msm_plan_destroy(self._p)
-            self._p = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
+        self._scalars_from_ntt(ntt_plan, offset)
 
 
 def keccak256_batch(msgs: bytes, offsets, n: int):

@@ -38,6 +38,29 @@ def test_all_header_symbols_exported():
         assert hasattr(lib, s), f"missing export: {s}"
 
 
+@pytest.mark.parametrize("cls,prefix,aff,jac", [
+    ("MsmPlan", "msm", 64, 96),
+    ("BlsMsmPlan", "bls_msm", 96, 144),
+    ("BlsG2MsmPlan", "bls_g2_msm", 192, 288),
+    ("Bn254G2MsmPlan", "bn254_g2_msm", 128, 192),
+])
+def test_msm_plan_classes_call_declared_exports(cls, prefix, aff, jac):
+    """every ethrex_mi355_<prefix>_<op> a plan class can call is in the
+    header (and so, by the test above, exported); an op outside the
+    class's list is refused before any lookup"""
+    import ethrex_amd.lib as lib
+    plan = getattr(lib, cls)
+    assert (plan._PREFIX, plan._AFF, plan._JAC) == (prefix, aff, jac)
+    syms = set(_header_symbols())
+    assert len(plan._OPS) >= 11 and len(set(plan._OPS)) == len(plan._OPS)
+    for op in plan._OPS:
+        name = f"ethrex_mi355_{prefix}_{op}"
+        assert name in syms, f"{cls}: {name} not in the header"
+        assert plan._fn(op) is not None
+    with pytest.raises(AttributeError):
+        plan._fn("no_such_op")
+
+
 def test_version():
     import ethrex_amd
     assert "gfx950" in ethrex_amd.version()

@@ -87,6 +87,40 @@ def test_gpu_bls_fixed_base_blob(gpu, oracle_mod):
     plan.destroy()
 
 
+def test_gpu_bls_async_with_and_without_table(gpu, oracle_mod):
+    """run_async()/sync() give run()'s bytes on the variable-base chain,
+    then, after precompute() swaps the point table under the captured
+    graphs, on the fixed-base chain, and again after new scalars."""
+    n = 4096
+    plan = gpu.BlsMsmPlan(n)
+    try:
+        plan.gen_points(0)
+        pts = plan.download_points()
+        scs = gpu.bls_gen_fr(42, n)
+        plan.upload_scalars(scs)
+        want = plan.run()
+        rc, ref = oracle_mod.bls_g1_msm(pts, scs, n)
+        assert rc == 0 and want == ref
+        for _ in range(3):
+            plan.run_async()
+        assert plan.sync() == want, "async, no table"
+        plan.precompute()
+        assert plan.run() == want, "run, table"
+        for _ in range(3):
+            plan.run_async()
+        assert plan.sync() == want, "async, table (recaptured)"
+        scs2 = gpu.bls_gen_fr(99, n)
+        plan.upload_scalars(scs2)
+        want2 = plan.run()
+        rc, ref2 = oracle_mod.bls_g1_msm(pts, scs2, n)
+        assert rc == 0 and want2 == ref2
+        for _ in range(2):
+            plan.run_async()
+        assert plan.sync() == want2, "async, table, new scalars"
+    finally:
+        plan.destroy()
+
+
 def test_gpu_bls_msm_parity_2_14(gpu, oracle_mod):
     n = 1 << 14
     plan = gpu.BlsMsmPlan(n)

@@ -4,7 +4,9 @@ T[w*n + i] = 2^(c*w) * P_i), forced with EM_MSM_FB at the smallest shapes
 at which the recode, the table or the walk can go wrong: n = 1, 2, 3,
 2^10 + 1 and 2^13, against the CPU oracle, bit-exact.  Also: every entry
 point agrees with the forced-off path byte for byte, sampled table rows
-equal 2^(c*w) * P_i, and a plan whose table cannot fit falls back.
+equal 2^(c*w) * P_i, and a plan whose table cannot fit falls back.  One
+case at n = 2^23 holds the separate-window path with 16-bit sort keys to
+the merged path, which is the default there.
 """
 import pytest
 
@@ -162,6 +164,44 @@ def test_fb_entry_points_match_forced_off(gpu, monkeypatch, base):
     assert res["0"][0] == res["0"][1] == res["0"][2]
     assert res["0"][3] == res["0"][4] != res["0"][0]
     assert res["22"] == res["0"]
+
+
+def test_keys16_window_path_matches_merged_2_23(gpu, monkeypatch):
+    """n = 2^23, the smallest size with 16-bit per-window sort keys: the
+    EM_MSM_FB=0 plan (u16 digits, one sort per window, segmented offsets)
+    gives, from run, run_async + sync and run_partial, the bytes of the
+    default plan, which runs merged c = 22 there (its own recode, sort
+    geometry and walk; pinned to the oracle by the small shapes above)."""
+    n = 1 << 23
+    scs = gpu.gen_fr(42, n)
+    monkeypatch.delenv("EM_MSM_FB", raising=False)
+    plan = gpu.MsmPlan(n)
+    try:
+        assert plan.fixed_base == 22
+        plan.gen_points(0)
+        plan.upload_scalars(scs)
+        want = plan.run()
+    finally:
+        plan.destroy()
+    monkeypatch.setenv("EM_MSM_FB", "0")
+    plan = gpu.MsmPlan(n)
+    try:
+        assert plan.fixed_base == 0
+        plan.gen_points(0)
+        plan.upload_scalars(scs)
+        assert plan.run() == want, "run()"
+        t = plan.last_times()
+        plan.run_async()
+        plan.run_async()
+        assert plan.sync() == want, "run_async()/sync()"
+        assert gpu.g1_combine_cpu(plan.run_partial(), 1) == want, "partial"
+    finally:
+        plan.destroy()
+    print("last_times (EM_MSM_FB=0, n=2^23):", t)
+    assert t["digits_sort_ms"] > 0
+    assert t["bucket_acc_ms"] > 0
+    assert t["reduce_ms"] > 0
+    assert t["total_ms"] >= t["bucket_acc_ms"]
 
 
 @pytest.mark.parametrize("c", CS)
