@@ -11,7 +11,8 @@ The product path FAILS LOUDLY if the HIP library is missing — there is no
 CPU fallback anywhere (DESIGN.md "Oracle discipline").
 """
 from .lib import (EM_OK, EM_ERR_POINT, EM_ERR_INPUT, EM_ERR_HIP,
-                  MsmPlan, NttPlan, QuotPlan, BlsMsmPlan, device_count,
+                  MsmPlan, NttPlan, QuotPlan, R1csPlan, BlsMsmPlan,
+                  device_count,
                   set_device, version, g1_add, g1_mul, g1_msm, fr_ntt,
                   coset_ntt, g1_combine,
                   g1_combine_cpu, gen_fr,
@@ -22,7 +23,8 @@ from .lib import (EM_OK, EM_ERR_POINT, EM_ERR_INPUT, EM_ERR_HIP,
 
 __all__ = [
     "EM_OK", "EM_ERR_POINT", "EM_ERR_INPUT", "EM_ERR_HIP",
-    "MsmPlan", "NttPlan", "QuotPlan", "BlsMsmPlan", "device_count",
+    "MsmPlan", "NttPlan", "QuotPlan", "R1csPlan", "BlsMsmPlan",
+    "device_count",
     "set_device", "version", "g1_add", "g1_mul", "g1_msm", "fr_ntt",
     "coset_ntt", "g1_combine",
     "g1_combine_cpu", "gen_fr",

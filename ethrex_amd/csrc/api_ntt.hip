@@ -15,6 +15,10 @@
 #include "../../include/ethrex_mi355.h"
 #include "ntt_kernels.h"
 #include "keccak_kernels.h"   // k_keccak_pair / k_wrap_expand (witness fill)
+#include "r1cs_kernels.h"     // sparse A z / B z / C z
+#include "r1cs_pack.h"        // host CSR validation + packing
+
+#include <vector>
 
 using namespace em;
 
@@ -798,5 +802,265 @@ extern "C" int ethrex_mi355_quot_last_times(em_quot_plan *q,
                                             double times_ms[5]) {
     if (!q || !times_ms) return EM_ERR_INPUT;
     memcpy(times_ms, q->last_ms, sizeof q->last_ms);
+    return EM_OK;
+}
+
+// ===================== R1CS evaluation (A z, B z, C z) =====================
+// y = M z for the three sparse constraint matrices of a circuit (DESIGN.md
+// "R1CS evaluation").  upload_matrix validates and repacks the CSR on the
+// host (r1cs_pack.h: setup, not a run); eval is two or three launches on
+// the null stream; the results are resident fe4m vectors that
+// ethrex_mi355_quot_load_device takes device to device.
+
+// short/long row threshold and long-row chunk: the measured defaults
+// (profiles/r1cs.md) or EM_R1CS_T / EM_R1CS_CHUNK, read once per process
+constexpr uint32_t R1CS_T_DEFAULT = 32;
+constexpr uint32_t R1CS_CHUNK_DEFAULT = 1024;
+struct r1cs_cfg {
+    uint32_t T, chunk;
+};
+static const r1cs_cfg &r1cs_config() {
+    static const r1cs_cfg c = [] {
+        r1cs_cfg v = {R1CS_T_DEFAULT, R1CS_CHUNK_DEFAULT};
+        if (const char *e = std::getenv("EM_R1CS_T")) {
+            long long t = atoll(e);
+            if (t >= 0) v.T = t > 0xffffffffll ? 0xffffffffu : (uint32_t)t;
+        }
+        if (const char *e = std::getenv("EM_R1CS_CHUNK")) {
+            long long t = atoll(e);
+            if (t >= 1 && t <= (1 << 24))
+                v.chunk = (uint32_t)((t + 63) / 64 * 64);
+        }
+        return v;
+    }();
+    return c;
+}
+
+struct r1cs_mat {
+    bool loaded = false;
+    bool has_y = false;
+    size_t n_rows = 0;
+    uint32_t n_slices = 0, n_chunks = 0, n_long = 0;
+    fe9 *d_dict = nullptr;
+    uint2 *d_s_ent = nullptr;
+    u64 *d_s_off = nullptr;
+    u32 *d_s_len = nullptr, *d_s_perm = nullptr;
+    uint2 *d_l_ent = nullptr;
+    r1cs_chk *d_l_chunk = nullptr;
+    u32 *d_l_chunk_off = nullptr, *d_l_row = nullptr;
+    fe9 *d_part = nullptr;
+    fe4 *d_y = nullptr;       // n results, allocated with the plan
+};
+
+struct em_r1cs_plan {
+    size_t n = 0, n_vars = 0;
+    fe4 *d_z = nullptr;
+    uint8_t *d_stage = nullptr;   // max(n, n_vars) * 32 bytes
+    uint32_t *d_err = nullptr;
+    bool has_z = false;
+    r1cs_mat m[3];
+    hipEvent_t ev[2];
+    int n_ev = 0;
+    double last_ms[3] = {0, 0, 0};
+};
+
+static void r1cs_mat_free(r1cs_mat &m) {
+    for (void *t : {(void *)m.d_dict, (void *)m.d_s_ent, (void *)m.d_s_off,
+                    (void *)m.d_s_len, (void *)m.d_s_perm, (void *)m.d_l_ent,
+                    (void *)m.d_l_chunk, (void *)m.d_l_chunk_off,
+                    (void *)m.d_l_row, (void *)m.d_part})
+        (void)hipFree(t);
+    m.d_dict = nullptr;
+    m.d_s_ent = m.d_l_ent = nullptr;
+    m.d_s_off = nullptr;
+    m.d_s_len = m.d_s_perm = m.d_l_chunk_off = m.d_l_row = nullptr;
+    m.d_l_chunk = nullptr;
+    m.d_part = nullptr;
+    m.loaded = m.has_y = false;
+}
+
+extern "C" int ethrex_mi355_r1cs_plan_create(size_t n, size_t n_vars,
+                                             em_r1cs_plan **plan) {
+    if (!plan || !ntt_size_ok(n) || n_vars == 0 ||
+        n_vars >= ((size_t)1 << 32))
+        return EM_ERR_INPUT;
+    int rc = require_gpu();
+    if (rc) return rc;
+    em_r1cs_plan *p = new em_r1cs_plan();
+    p->n = n;
+    p->n_vars = n_vars;
+    hipError_t e = hipMalloc((void **)&p->d_z, n_vars * sizeof(fe4));
+    if (e == hipSuccess)
+        e = hipMalloc((void **)&p->d_stage, (n > n_vars ? n : n_vars) * 32);
+    if (e == hipSuccess) e = hipMalloc((void **)&p->d_err, 4);
+    for (int w = 0; w < 3 && e == hipSuccess; w++)
+        e = hipMalloc((void **)&p->m[w].d_y, n * sizeof(fe4));
+    for (; p->n_ev < 2 && e == hipSuccess; p->n_ev++)
+        e = hipEventCreate(&p->ev[p->n_ev]);
+    if (e != hipSuccess) {
+        if (p->n_ev) p->n_ev--;   // the failed slot holds no event
+        rc = hip_fail(e, "r1cs_plan_create");
+        ethrex_mi355_r1cs_plan_destroy(p);
+        return rc;
+    }
+    *plan = p;
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_r1cs_plan_destroy(em_r1cs_plan *p) {
+    if (!p) return EM_ERR_INPUT;
+    for (r1cs_mat &m : p->m) {
+        r1cs_mat_free(m);
+        (void)hipFree(m.d_y);
+    }
+    (void)hipFree(p->d_z);
+    (void)hipFree(p->d_stage);
+    (void)hipFree(p->d_err);
+    for (int i = 0; i < p->n_ev; i++) (void)hipEventDestroy(p->ev[i]);
+    delete p;
+    return EM_OK;
+}
+
+// *dst = device copy of `count` elements of src (nothing for count == 0)
+template <typename D, typename S>
+static int r1cs_to_device(D **dst, const S *src, size_t count) {
+    static_assert(sizeof(D) == sizeof(S), "same layout");
+    if (count == 0) return EM_OK;
+    HIP_TRY(hipMalloc((void **)dst, count * sizeof(D)));
+    HIP_TRY(hipMemcpy(*dst, src, count * sizeof(D), hipMemcpyHostToDevice));
+    return EM_OK;
+}
+
+static int r1cs_mat_to_device(r1cs_mat &m, const em_r1cs::r1cs_packed &pk) {
+    // dictionary: canonical words -> fe9 Montgomery (host; upload is setup)
+    std::vector<fe9> dict(pk.dict.size());
+    for (size_t i = 0; i < dict.size(); i++)
+        dict[i] = to_mont9<Fr9T>(fe9_from_u64x4(pk.dict[i].data()));
+    int rc;
+    if ((rc = r1cs_to_device(&m.d_dict, dict.data(), dict.size()))) return rc;
+    if ((rc = r1cs_to_device(&m.d_s_ent, pk.s_ent.data(), pk.s_ent.size())))
+        return rc;
+    if ((rc = r1cs_to_device(&m.d_s_off, pk.s_off.data(), pk.s_off.size())))
+        return rc;
+    if ((rc = r1cs_to_device(&m.d_s_len, pk.s_len.data(), pk.s_len.size())))
+        return rc;
+    if ((rc = r1cs_to_device(&m.d_s_perm, pk.s_perm.data(), pk.s_perm.size())))
+        return rc;
+    if ((rc = r1cs_to_device(&m.d_l_ent, pk.l_ent.data(), pk.l_ent.size())))
+        return rc;
+    if ((rc = r1cs_to_device(&m.d_l_chunk, pk.l_chunk.data(),
+                             pk.l_chunk.size()))) return rc;
+    if ((rc = r1cs_to_device(&m.d_l_chunk_off, pk.l_chunk_off.data(),
+                             pk.l_chunk_off.size()))) return rc;
+    if ((rc = r1cs_to_device(&m.d_l_row, pk.l_row.data(), pk.l_row.size())))
+        return rc;
+    if (!pk.l_chunk.empty())
+        HIP_TRY(hipMalloc((void **)&m.d_part, pk.l_chunk.size() * sizeof(fe9)));
+    m.n_rows = pk.n_rows;
+    m.n_slices = (uint32_t)pk.n_slices();
+    m.n_chunks = (uint32_t)pk.l_chunk.size();
+    m.n_long = (uint32_t)pk.l_row.size();
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_r1cs_upload_matrix(em_r1cs_plan *p, int which,
+                                               const uint64_t *row_offs,
+                                               const uint32_t *cols,
+                                               const uint8_t *coeffs32,
+                                               size_t n_rows) {
+    if (!p || which < 0 || which > 2) return EM_ERR_INPUT;
+    r1cs_mat &m = p->m[which];
+    r1cs_mat_free(m);             // unloaded until the new one is in place
+    const r1cs_cfg &cfg = r1cs_config();
+    em_r1cs::r1cs_packed pk;
+    int rc = em_r1cs::r1cs_pack(row_offs, cols, coeffs32, n_rows, p->n,
+                                p->n_vars, cfg.T, cfg.chunk, pk);
+    if (rc) return EM_ERR_INPUT;
+    rc = r1cs_mat_to_device(m, pk);
+    if (rc) {
+        r1cs_mat_free(m);
+        return rc;
+    }
+    m.loaded = true;
+    return EM_OK;
+}
+
+static void r1cs_new_witness(em_r1cs_plan *p, bool ok) {
+    p->has_z = ok;
+    for (r1cs_mat &m : p->m) m.has_y = false;
+}
+
+extern "C" int ethrex_mi355_r1cs_upload_witness(em_r1cs_plan *p,
+                                                const uint8_t *z32) {
+    if (!p || !z32) return EM_ERR_INPUT;
+    r1cs_new_witness(p, false);
+    int rc = fr_upload_be(z32, p->n_vars, p->d_stage, p->d_z, p->d_err);
+    if (rc) return rc;
+    r1cs_new_witness(p, true);
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_r1cs_witness_from_device(em_r1cs_plan *p,
+                                                     const void *d_fe4m,
+                                                     uint64_t offset) {
+    if (!p || !d_fe4m) return EM_ERR_INPUT;
+    r1cs_new_witness(p, false);
+    HIP_TRY(hipMemcpy(p->d_z, (const fe4 *)d_fe4m + offset,
+                      p->n_vars * sizeof(fe4), hipMemcpyDeviceToDevice));
+    r1cs_new_witness(p, true);
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_r1cs_eval(em_r1cs_plan *p, int which) {
+    if (!p || which < 0 || which > 2) return EM_ERR_INPUT;
+    r1cs_mat &m = p->m[which];
+    if (!m.loaded || !p->has_z) return EM_ERR_INPUT;
+    m.has_y = false;
+    HIP_TRY(hipEventRecord(p->ev[0], 0));
+    if (m.n_rows < p->n)
+        HIP_TRY(hipMemsetAsync(m.d_y + m.n_rows, 0,
+                               (p->n - m.n_rows) * sizeof(fe4), 0));
+    if (m.n_slices)
+        hipLaunchKernelGGL(k_r1cs_rows_sell, dim3(blocks_for(m.n_slices, 4)),
+                           dim3(256), 0, 0, m.d_s_ent, m.d_s_off, m.d_s_len,
+                           m.d_s_perm, m.n_slices, m.d_dict, p->d_z, m.d_y);
+    if (m.n_chunks) {
+        hipLaunchKernelGGL(k_r1cs_rows_long, dim3(blocks_for(m.n_chunks, 4)),
+                           dim3(256), 0, 0, m.d_l_ent, m.d_l_chunk, m.n_chunks,
+                           m.d_dict, p->d_z, m.d_part);
+        hipLaunchKernelGGL(k_r1cs_long_sum, dim3(blocks_for(m.n_long, 4)),
+                           dim3(256), 0, 0, m.d_part, m.d_l_chunk_off,
+                           m.d_l_row, m.n_long, m.d_y);
+    }
+    HIP_TRY(hipEventRecord(p->ev[1], 0));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    float ms;
+    HIP_TRY(hipEventElapsedTime(&ms, p->ev[0], p->ev[1]));
+    p->last_ms[which] = ms;
+    m.has_y = true;
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_r1cs_download(em_r1cs_plan *p, int which,
+                                          uint8_t *elems32) {
+    if (!p || !elems32 || which < 0 || which > 2 || !p->m[which].has_y)
+        return EM_ERR_INPUT;
+    return fr_download_be(elems32, p->n, p->m[which].d_y, p->d_stage);
+}
+
+extern "C" int ethrex_mi355_r1cs_device_data(em_r1cs_plan *p, int which,
+                                             const void **ptr, size_t *n) {
+    if (!p || !ptr || which < 0 || which > 2 || !p->m[which].has_y)
+        return EM_ERR_INPUT;
+    *ptr = p->m[which].d_y;
+    if (n) *n = p->n;
+    return EM_OK;
+}
+
+extern "C" int ethrex_mi355_r1cs_last_times(em_r1cs_plan *p,
+                                            double times_ms[3]) {
+    if (!p || !times_ms) return EM_ERR_INPUT;
+    memcpy(times_ms, p->last_ms, sizeof p->last_ms);
     return EM_OK;
 }

@@ -4,6 +4,7 @@ Loads the in-tree shared library built by __graft_entry__.build().  Import
 fails loudly if the library is absent: the product path never falls back
 to CPU.
 """
+import array
 import ctypes
 import os
 
@@ -38,7 +39,10 @@ for _f in ("device_count", "set_device", "bn254_g1_add", "bn254_g1_mul",
            "ntt_run_coset", "bn254_fr_coset_ntt", "quot_plan_create",
            "quot_plan_destroy", "quot_upload", "quot_load_device",
            "quot_mul_ab_into_c", "quot_run", "quot_download",
-           "quot_device_data", "quot_last_times"):
+           "quot_device_data", "quot_last_times", "r1cs_plan_create",
+           "r1cs_plan_destroy", "r1cs_upload_matrix", "r1cs_upload_witness",
+           "r1cs_witness_from_device", "r1cs_eval", "r1cs_download",
+           "r1cs_device_data", "r1cs_last_times"):
     getattr(_lib, f"ethrex_mi355_{_f}").restype = ctypes.c_int
 
 
@@ -397,6 +401,16 @@ class QuotPlan:
         _check(_lib.ethrex_mi355_quot_load_device(
             self._p, ctypes.c_int(which), ptr), "quot_load_device")
 
+    def load_from_r1cs(self, which: int, rplan, matrix: int):
+        """copy an R1csPlan result (matrix 0 = A z, 1 = B z, 2 = C z) into a
+        slot, device to device"""
+        ptr, nn = rplan.device_data(matrix)
+        if nn != self.n:
+            raise HipCoreError(EM_ERR_INPUT,
+                               f"quot_load_from_r1cs: size {nn} != {self.n}")
+        _check(_lib.ethrex_mi355_quot_load_device(
+            self._p, ctypes.c_int(which), ptr), "quot_load_device")
+
     def mul_ab_into_c(self):
         _check(_lib.ethrex_mi355_quot_mul_ab_into_c(self._p),
                "quot_mul_ab_into_c")
@@ -431,6 +445,114 @@ class QuotPlan:
     def destroy(self):
         if self._p:
             _lib.ethrex_mi355_quot_plan_destroy(self._p)
+            self._p = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class R1csPlan:
+    """Device-resident R1CS evaluation: the three sparse constraint
+    matrices A, B, C (which = 0, 1, 2; CSR, uploaded once and repacked on
+    the host) times the witness vector z of n_vars elements.  The results
+    are n resident elements each (rows past the matrix are zero) and feed
+    QuotPlan.load_from_r1cs without leaving the device."""
+
+    def __init__(self, n: int, n_vars: int):
+        self.n = n
+        self.n_vars = n_vars
+        self._p = ctypes.c_void_p()
+        _check(_lib.ethrex_mi355_r1cs_plan_create(
+            ctypes.c_size_t(n), ctypes.c_size_t(n_vars),
+            ctypes.byref(self._p)), "r1cs_plan_create")
+
+    def upload_matrix(self, which: int, row_offs, cols, coeffs_bytes: bytes):
+        """row_offs: n_rows + 1 offsets; cols: nnz column indices;
+        coeffs_bytes: nnz 32-byte big-endian canonical coefficients"""
+        try:
+            row_offs = array.array("Q", row_offs)
+            cols = array.array("I", cols)
+        except (OverflowError, TypeError):
+            raise HipCoreError(EM_ERR_INPUT,
+                               "r1cs_upload_matrix: offsets are u64, "
+                               "columns u32") from None
+        if not row_offs:
+            raise HipCoreError(EM_ERR_INPUT,
+                               "r1cs_upload_matrix: row_offs is empty")
+        if len(coeffs_bytes) != 32 * len(cols):
+            raise HipCoreError(EM_ERR_INPUT,
+                               f"r1cs_upload_matrix: need {32 * len(cols)} "
+                               "coefficient bytes")
+        if row_offs[-1] != len(cols):
+            raise HipCoreError(EM_ERR_INPUT,
+                               f"r1cs_upload_matrix: {len(cols)} columns for "
+                               f"{row_offs[-1]} entries")
+        n_rows = len(row_offs) - 1
+        offs = (ctypes.c_uint64 * len(row_offs)).from_buffer(row_offs)
+        # one spare element keeps the pointers of an empty matrix non-null
+        cols.append(0)
+        carr = (ctypes.c_uint32 * len(cols)).from_buffer(cols)
+        _check(_lib.ethrex_mi355_r1cs_upload_matrix(
+            self._p, ctypes.c_int(which), offs, carr,
+            _buf(coeffs_bytes + b"\x00"),
+            ctypes.c_size_t(n_rows)), "r1cs_upload_matrix")
+
+    def upload_witness(self, z_bytes: bytes):
+        if len(z_bytes) != 32 * self.n_vars:
+            raise HipCoreError(EM_ERR_INPUT,
+                               f"r1cs_upload_witness: need "
+                               f"{32 * self.n_vars} bytes")
+        _check(_lib.ethrex_mi355_r1cs_upload_witness(self._p, _buf(z_bytes)),
+               "r1cs_upload_witness")
+
+    def witness_from(self, src, offset: int = 0):
+        """take z from n_vars resident elements of any plan with a
+        device_data() -> (ptr, n) accessor, at element `offset`"""
+        ptr, nn = src.device_data()
+        if offset < 0 or offset + self.n_vars > nn:
+            raise HipCoreError(EM_ERR_INPUT,
+                               f"r1cs_witness_from: offset {offset} + n_vars "
+                               f"{self.n_vars} exceeds source size {nn}")
+        _check(_lib.ethrex_mi355_r1cs_witness_from_device(
+            self._p, ptr, ctypes.c_uint64(offset)),
+            "r1cs_witness_from_device")
+
+    def eval(self, which: int):
+        _check(_lib.ethrex_mi355_r1cs_eval(self._p, ctypes.c_int(which)),
+               "r1cs_eval")
+
+    def eval_all(self):
+        for which in range(3):
+            self.eval(which)
+
+    def download(self, which: int) -> bytes:
+        out = (ctypes.c_uint8 * (32 * self.n))()
+        _check(_lib.ethrex_mi355_r1cs_download(self._p, ctypes.c_int(which),
+                                               out), "r1cs_download")
+        return bytes(out)
+
+    def device_data(self, which: int):
+        """(device pointer, n) of M_which z (fe4m); valid until the next
+        eval / upload_matrix of that matrix or destroy"""
+        ptr = ctypes.c_void_p()
+        nn = ctypes.c_size_t(0)
+        _check(_lib.ethrex_mi355_r1cs_device_data(
+            self._p, ctypes.c_int(which), ctypes.byref(ptr),
+            ctypes.byref(nn)), "r1cs_device_data")
+        return ptr, nn.value
+
+    def last_times(self):
+        t = (ctypes.c_double * 3)()
+        _check(_lib.ethrex_mi355_r1cs_last_times(self._p, t),
+               "r1cs_last_times")
+        return {"a_ms": t[0], "b_ms": t[1], "c_ms": t[2]}
+
+    def destroy(self):
+        if self._p:
+            _lib.ethrex_mi355_r1cs_plan_destroy(self._p)
             self._p = ctypes.c_void_p()
 
     def __del__(self):

@@ -99,7 +99,12 @@ class Mi355Backend:
     core's composition output, carried through the §8f row-3 wire)."""
 
     BINDINGS = ("seed", "witness")
-    COMPOSITIONS = ("direct", "quotient")
+    COMPOSITIONS = ("direct", "quotient", "r1cs")
+    # composition="r1cs": product-chain circuit v1 (ethrex_amd/r1cs.py) with
+    # n constraints, 64 free inputs, 3 entries per A/B row, this circuit seed
+    R1CS_K = 64
+    R1CS_FAN_IN = 3
+    R1CS_SEED = 0x72316373   # "r1cs"
 
     def __init__(self, msm_log2=16, ntt_log2=12, device=0, binding="seed",
                  composition="direct"):
@@ -119,6 +124,11 @@ class Mi355Backend:
         #                c = a (.) b on device, and the quotient polynomial
         #                h = (A*B - C) / (X^n - 1) (QuotPlan; DESIGN.md
         #                "Quotient polynomial") is the MSM's scalar vector.
+        #   "r1cs"     — a satisfied constraint system end to end: the
+        #                first 64 elements of the input vector are the free
+        #                inputs of product-chain circuit v1, a = A z, b = B z,
+        #                c = C z are evaluated on device (R1csPlan) and feed
+        #                the quotient, whose h is the MSM's scalar vector.
         if composition not in self.COMPOSITIONS:
             raise BackendError(f"mi355: unknown composition {composition!r} "
                                f"(expected one of {self.COMPOSITIONS})")
@@ -211,10 +221,11 @@ class Mi355Backend:
         # primitives this core exists for, composed as the Groth16 wrap
         # composes them, with no PCIe hop between them.
         n = 1 << self.msm_log2
-        if self.composition == "quotient":
+        if self.composition in ("quotient", "r1cs"):
+            run = (self._prove_quotient if self.composition == "quotient"
+                   else self._prove_r1cs)
             try:
-                msm_out, ntt_out = self._prove_quotient(
-                    ea, n, seed, statement, kplans)
+                msm_out, ntt_out = run(ea, n, seed, statement, kplans)
             finally:
                 for kp in kplans or ():
                     kp.destroy()
@@ -279,6 +290,47 @@ class Mi355Backend:
             qplan.destroy()
             if nplan is not None:
                 nplan.destroy()
+
+    def _prove_r1cs(self, ea, n, seed, statement, kplans):
+        """composition="r1cs": z on the host from 64 free inputs, A z, B z,
+        C z on device, device-to-device into the quotient, h feeds the MSM.
+        Returns (MSM result, h bytes)."""
+        from . import r1cs as C
+        k = self.R1CS_K
+        if n < k:
+            raise BackendError("mi355: composition r1cs needs msm_log2 >= 6")
+        if kplans:
+            nplan = ea.NttPlan(n)
+            try:
+                nplan.fill_from_digests(
+                    kplans[-1], bytes.fromhex(statement["commitment"]))
+                free = nplan.download()[:32 * k]
+            finally:
+                nplan.destroy()
+        else:
+            free = ea.gen_fr(seed, k)
+        mats, witness = C.chain_circuit(n, k, self.R1CS_FAN_IN,
+                                        self.R1CS_SEED)
+        z = witness([int.from_bytes(free[32 * i:32 * i + 32], "big")
+                     for i in range(k)])
+        plan = ea.MsmPlan(n)
+        qplan = ea.QuotPlan(n)
+        rplan = ea.R1csPlan(n, len(z))
+        try:
+            plan.gen_points(0)
+            for which, (offs, cols, coeffs) in enumerate(mats):
+                rplan.upload_matrix(which, offs, cols, C.fr_bytes(coeffs))
+            rplan.upload_witness(C.fr_bytes(z))
+            rplan.eval_all()
+            for which in range(3):
+                qplan.load_from_r1cs(which, rplan, which)
+            qplan.run()
+            plan.scalars_from_ntt(qplan, 0)
+            return plan.run(), qplan.download()
+        finally:
+            plan.destroy()
+            qplan.destroy()
+            rplan.destroy()
 
     def verify(self, proof) -> None:
         if len(proof.get("msm", b"")) != 64:

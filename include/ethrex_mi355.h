@@ -232,6 +232,49 @@ int ethrex_mi355_quot_device_data(em_quot_plan *plan, const void **ptr,
 /* [0]=3 iNTT, [1]=3 coset NTT, [2]=pointwise, [3]=coset iNTT, [4]=total (ms) */
 int ethrex_mi355_quot_last_times(em_quot_plan *plan, double times_ms[5]);
 
+/* ---- R1CS evaluation: y = M z for the three sparse constraint matrices
+ * A, B, C of a Groth16 circuit and the witness vector z (DESIGN.md "R1CS
+ * evaluation").  The matrices are uploaded once in CSR form and repacked
+ * on the host; the results are resident fe4m vectors that feed
+ * ethrex_mi355_quot_load_device without leaving the device.
+ *   y_i = sum_k coeff_k * z[col_k] mod r over the entries of row i; a
+ *   column may repeat in a row (its terms add), a zero coefficient is
+ *   legal, an empty row gives 0, n_rows = 0 gives the zero vector.
+ * EM_ERR_INPUT: null pointer, bad n, n_vars == 0 or >= 2^32, `which`
+ * outside 0..2, n_rows > n, row_offs[0] != 0 or a decreasing offset,
+ * nnz >= 2^32, a column >= n_vars, a non-canonical coefficient or witness
+ * element, eval before both that matrix and a witness are loaded, download
+ * / device_data before an eval of that matrix since its last upload (or
+ * since the last witness change).  A failed upload leaves that matrix (or
+ * the witness) unloaded.  EM_R1CS_T (short/long row threshold) and
+ * EM_R1CS_CHUNK (long-row chunk, a multiple of 64) override the packing
+ * constants; both are read once per process. ---- */
+typedef struct em_r1cs_plan em_r1cs_plan;
+/* n: evaluation-domain size (power of two <= 2^28, the QuotPlan rule);
+ * n_vars: length m of the witness vector z, 1 <= m < 2^32 */
+int ethrex_mi355_r1cs_plan_create(size_t n, size_t n_vars, em_r1cs_plan **plan);
+int ethrex_mi355_r1cs_plan_destroy(em_r1cs_plan *plan);
+/* which: 0 = A, 1 = B, 2 = C.  CSR: row_offs[n_rows+1] (u64, row_offs[0] = 0,
+ * non-decreasing), cols[nnz] (u32, < n_vars), coeffs32[nnz] 32-B big-endian
+ * canonical Fr.  n_rows <= n; rows [n_rows, n) of the result are zero. */
+int ethrex_mi355_r1cs_upload_matrix(em_r1cs_plan *plan, int which,
+        const uint64_t *row_offs, const uint32_t *cols,
+        const uint8_t *coeffs32, size_t n_rows);
+int ethrex_mi355_r1cs_upload_witness(em_r1cs_plan *plan, const uint8_t *z32);
+/* take z from n_vars resident fe4m elements at element `offset` of a device
+ * vector (ethrex_mi355_ntt_device_data / quot_device_data) */
+int ethrex_mi355_r1cs_witness_from_device(em_r1cs_plan *plan,
+        const void *d_fe4m, uint64_t offset);
+/* y_which = M_which * z; synchronous */
+int ethrex_mi355_r1cs_eval(em_r1cs_plan *plan, int which);
+int ethrex_mi355_r1cs_download(em_r1cs_plan *plan, int which, uint8_t *elems32);
+/* device pointer to the n fe4m results, valid until the next eval of that
+ * matrix, upload_matrix(which) or destroy; feeds ethrex_mi355_quot_load_device */
+int ethrex_mi355_r1cs_device_data(em_r1cs_plan *plan, int which,
+        const void **ptr, size_t *n);
+/* HIP-event time of the last eval of A, B, C (ms; 0 if never run) */
+int ethrex_mi355_r1cs_last_times(em_r1cs_plan *plan, double times_ms[3]);
+
 /* ---- deterministic input generation (host-side; the product restatement
  *      of BASELINE.md's xoshiro256++/splitmix64 scheme; parity-tested
  *      against the oracle's independent restatement) ---- */
