@@ -22,6 +22,7 @@
 #include "gpu_field.h"
 #include "gpu_g1_9.h"
 #include "msm_kernels.h"
+#include "msm_fbm_partition_kernels.h"
 
 using namespace em;
 
@@ -64,6 +65,10 @@ struct msm_plan_t {
     uint64_t fb_table_bytes = 0;
     uint32_t *d_fb_boff = nullptr;    // per-bucket offsets (NBUCKETS + 1)
     g1jT<C> *d_fb_slots = nullptr;    // per-slot walk results (NSLOT)
+    // bucket partition (msm_fbm_partition.h) in place of the pair sort:
+    // unit size T, or 0 = the rocPRIM chain (EM_MSM_FBM_SORT=rocprim)
+    uint32_t fbp_tile = 0;
+    uint32_t *d_fbp = nullptr;        // pass counters, offsets, unit scans
     uint8_t *d_inf = nullptr;
     fe4 *d_scalars = nullptr;
     uint8_t *d_scratch = nullptr;     // PB*n bytes: point/scalar byte staging
@@ -148,6 +153,7 @@ static int msm_destroy_t(msm_plan_t<C> *p) {
     (void)hipFree(p->d_pts_ext);
     (void)hipFree(p->d_fb_boff);
     (void)hipFree(p->d_fb_slots);
+    (void)hipFree(p->d_fbp);
     (void)hipFree(p->d_inf);
     (void)hipFree(p->d_scalars);
     (void)hipFree(p->d_scratch);
@@ -199,6 +205,27 @@ static int msm_destroy_t(msm_plan_t<C> *p) {
 // values next to the sign bits, so NWIN_REAL * n must stay below 2^30.
 constexpr int FBM_DEFAULT_C = 22;
 constexpr size_t FBM_MIN_N = (size_t)1 << 23;
+
+// d_fbp layout for 2^IB buckets, in u32 words: the bin counters of passes A
+// and B (adjacent: zeroed by one launch), their scans, and the unit counts
+// and unit offsets that passes B and C share
+struct fbp_layout {
+    size_t cnt_a, cnt_b, off_a, off_b, ucnt, uoff, words;
+};
+static inline fbp_layout fbp_lay(uint32_t nbuckets) {
+    const size_t na = (size_t)(nbuckets >> 16) + 1;   // NBIN_A + 1
+    const size_t nc = (size_t)(nbuckets >> 8) + 1;    // NREG_C + 1
+    fbp_layout l;
+    l.cnt_a = 0;
+    l.cnt_b = na;
+    l.off_a = na + nc;
+    l.off_b = 2 * na + nc;
+    l.ucnt = 2 * na + 2 * nc;
+    l.uoff = 2 * na + 3 * nc;
+    l.words = 2 * na + 4 * nc;
+    return l;
+}
+static inline size_t fbp_words(uint32_t nbuckets) { return fbp_lay(nbuckets).words; }
 
 template <typename FN>
 static int fbm_dispatch(int c, FN fn) {
@@ -336,6 +363,18 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
         if (L < 8) L = 8;
         p->fb_chunk = (uint32_t)L;
         while ((L >> p->fb_len_bits) != 0) p->fb_len_bits++;
+        // stage 1 groups by bucket with the partition unless
+        // EM_MSM_FBM_SORT=rocprim asks for the pair sort (A/B, fallback);
+        // EM_MSM_FBM_TILE sets the unit size (tests: many units per region)
+        const char *sv = std::getenv("EM_MSM_FBM_SORT");
+        if (sv == nullptr || std::strcmp(sv, "rocprim") != 0) {
+            size_t T = FBP_TILE_DEFAULT;
+            if (const char *tv = std::getenv("EM_MSM_FBM_TILE"))
+                T = (size_t)strtoull(tv, nullptr, 10);
+            if (T < 1) T = 1;
+            if (T > FBP_TILE_MAX) T = FBP_TILE_MAX;
+            p->fbp_tile = (uint32_t)T;
+        }
     }
     const size_t kb = p->keys16 ? 2 : 4;
     hipError_t e = hipSuccess;
@@ -370,6 +409,8 @@ static int msm_create_t(size_t n, msm_plan_t<C> **plan) {
                                         p->d_loff[0], 0u,
                                         (size_t)nbuckets + 1);
         if (e == hipSuccess) e = hipMalloc(&p->d_scan_tmp, p->scan_tmp_bytes);
+        // partition counters: the largest scan is the one sized above
+        if (p->fbp_tile) mal((void **)&p->d_fbp, fbp_words(nbuckets) * 4);
     }
     mal((void **)&p->d_seg_sum, (size_t)nseg_tot * sizeof(g1jT<C>));
     mal((void **)&p->d_seg_wsum, (size_t)nseg_tot * sizeof(g1jT<C>));
@@ -753,6 +794,78 @@ static int msm_split_pct() {
     return pct;
 }
 
+// Stage 1 of the merged fixed-base mode, grouping: the three-pass bucket
+// partition (msm_fbm_partition_kernels.h).  Leaves sb[par].vals_out grouped
+// by bucket id and d_fb_boff[0..NBUCKETS], as the pair sort + k_offsets do.
+// Intermediates live in buffers the pair sort would use: pass A writes u16
+// keys to d_keys and values to d_vals, pass B writes u8 keys behind the u16
+// keys (d_keys holds 4 bytes per entry) and values to sb[par].keys_out.
+// All sizes given to rocPRIM and every grid are host constants.
+template <typename C, typename CFG>
+static hipError_t fbm_enqueue_partition(msm_plan_t<C> *p, int par,
+                                        hipStream_t st) {
+    using G = fbp_geom<CFG::IB>;
+    const msm_step_bufs &b = p->sb[par];
+    const size_t total = p->n * (size_t)CFG::NWIN_REAL;
+    const uint32_t T = p->fbp_tile;
+    const fbp_layout l = fbp_lay(G::NBUCKETS);
+    uint32_t *cnt_a = p->d_fbp + l.cnt_a, *cnt_b = p->d_fbp + l.cnt_b;
+    uint32_t *off_a = p->d_fbp + l.off_a, *off_b = p->d_fbp + l.off_b;
+    uint32_t *ucnt = p->d_fbp + l.ucnt, *uoff = p->d_fbp + l.uoff;
+    uint32_t *cnt_c = p->d_cnt;       // NBUCKETS + 1; stage 1 reuses it after
+    uint16_t *k16 = (uint16_t *)p->d_keys;
+    uint8_t *k8 = (uint8_t *)p->d_keys + total * 2;
+    uint32_t *v1 = p->d_vals, *v2 = b.keys_out;
+    auto scan = [&](uint32_t *in, uint32_t *out, size_t len) {
+        size_t stmp = p->scan_tmp_bytes;
+        return rocprim::exclusive_scan(p->d_scan_tmp, stmp, in, out, 0u, len,
+                                       rocprim::plus<uint32_t>(), st);
+    };
+    auto units = [&](const uint32_t *off, uint32_t regions) {
+        hipLaunchKernelGGL((k_fbp_unit_counts<CFG>),
+                           dim3(blocks_for((size_t)regions + 1, 256)),
+                           dim3(256), 0, st, off, regions, T, ucnt);
+        return scan(ucnt, uoff, (size_t)regions + 1);
+    };
+    const uint32_t nab = (uint32_t)(l.off_a - l.cnt_a);   // cnt_a and cnt_b
+    hipLaunchKernelGGL((k_fbp_zero<CFG>), dim3(blocks_for(nab, 256)),
+                       dim3(256), 0, st, cnt_a, nab);
+    hipLaunchKernelGGL((k_fbp_zero<CFG>),
+                       dim3(blocks_for((size_t)G::NBUCKETS + 1, 256)),
+                       dim3(256), 0, st, cnt_c, G::NBUCKETS + 1);
+    // pass A: scalars -> (u16, u32) in NBIN_A bins
+    hipLaunchKernelGGL((k_fbp_count_a<CFG>),
+                       dim3(blocks_for(p->n, FBP_BLOCK * FBP_A_SPT)),
+                       dim3(FBP_BLOCK), 0, st, p->d_scalars, p->d_inf, p->n,
+                       cnt_a);
+    EM_HT(scan(cnt_a, off_a, (size_t)G::NBIN_A + 1));
+    hipLaunchKernelGGL((k_fbp_scatter_a<CFG>),
+                       dim3(blocks_for(p->n, FBP_BLOCK)), dim3(FBP_BLOCK), 0,
+                       st, p->d_scalars, p->d_inf, p->n, cnt_a, off_a, k16, v1);
+    // pass B: regions = pass A's bins -> (u8, u32)
+    EM_HT(units(off_a, G::NREG_B));
+    const dim3 grid_b(fbp_grid(total, T, G::NREG_B));
+    hipLaunchKernelGGL((k_fbp_count<uint16_t, FBP_SHIFT_B>), grid_b,
+                       dim3(FBP_BLOCK), 0, st, k16, off_a, uoff, G::NREG_B, T,
+                       cnt_b);
+    EM_HT(scan(cnt_b, off_b, (size_t)G::NREG_C + 1));
+    hipLaunchKernelGGL((k_fbp_scatter<uint16_t, uint8_t, FBP_SHIFT_B, true>),
+                       grid_b, dim3(FBP_BLOCK), (size_t)T * 6, st, k16, v1,
+                       off_a, uoff, G::NREG_B, T, cnt_b, off_b, k8, v2);
+    // pass C: regions = pass B's bins -> values; its scan is d_fb_boff
+    EM_HT(units(off_b, G::NREG_C));
+    const dim3 grid_c(fbp_grid(total, T, G::NREG_C));
+    hipLaunchKernelGGL((k_fbp_count<uint8_t, FBP_SHIFT_C>), grid_c,
+                       dim3(FBP_BLOCK), 0, st, k8, off_b, uoff, G::NREG_C, T,
+                       cnt_c);
+    EM_HT(scan(cnt_c, p->d_fb_boff, (size_t)G::NBUCKETS + 1));
+    hipLaunchKernelGGL((k_fbp_scatter<uint8_t, uint8_t, FBP_SHIFT_C, false>),
+                       grid_c, dim3(FBP_BLOCK), (size_t)T * 5, st, k8, v2,
+                       off_b, uoff, G::NREG_C, T, cnt_c, p->d_fb_boff,
+                       (uint8_t *)nullptr, b.vals_out);
+    return hipSuccess;
+}
+
 // Stage 1, sort chain: scalar digits -> radix sort by bucket -> bucket
 // offsets -> length-sorted walk schedule (kills wave divergence in the walk).
 template <typename C, typename CFG>
@@ -767,15 +880,21 @@ static hipError_t msm_enqueue_sort_chain(msm_plan_t<C> *p, int par,
         const size_t total = p->n * (size_t)CFG::NWIN_REAL;
         constexpr uint32_t NB = CFG::NBUCKETS, NS = CFG::NSLOT;
         uint32_t *coff = p->d_loff[par];
-        hipLaunchKernelGGL((k_fbm_digits<CFG>), dim3(blocks_for(p->n, 256)),
-                           dim3(256), 0, st, p->d_scalars, p->d_inf,
-                           p->d_keys, p->d_vals, p->n);
-        EM_HT(rocprim::radix_sort_pairs(p->d_sort_tmp, tmp, p->d_keys,
-                                        b.keys_out, p->d_vals, b.vals_out,
-                                        total, 0, CFG::SORT_BITS, st));
-        hipLaunchKernelGGL((k_offsets<CFG>),
-                           dim3(blocks_for((size_t)NB + 1, 256)), dim3(256), 0,
-                           st, b.keys_out, total, p->d_fb_boff);
+        if (p->fbp_tile) {
+            EM_HT((fbm_enqueue_partition<C, CFG>(p, par, st)));
+        } else {
+            hipLaunchKernelGGL((k_fbm_digits<CFG>),
+                               dim3(blocks_for(p->n, 256)), dim3(256), 0, st,
+                               p->d_scalars, p->d_inf, p->d_keys, p->d_vals,
+                               p->n);
+            EM_HT(rocprim::radix_sort_pairs(p->d_sort_tmp, tmp, p->d_keys,
+                                            b.keys_out, p->d_vals, b.vals_out,
+                                            total, 0, CFG::SORT_BITS, st));
+            hipLaunchKernelGGL((k_offsets<CFG>),
+                               dim3(blocks_for((size_t)NB + 1, 256)),
+                               dim3(256), 0, st, b.keys_out, total,
+                               p->d_fb_boff);
+        }
         hipLaunchKernelGGL((k_fbm_chunk_counts<CFG>),
                            dim3(blocks_for((size_t)NB + 1, 256)), dim3(256), 0,
                            st, p->d_fb_boff, p->d_cnt, p->fb_chunk);
